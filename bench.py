@@ -16,7 +16,15 @@ launch time vs the 8 TB/s HBM peak.  cpu_baseline: the plain-C restatement of th
 sequential Riccati (oracle/kkt_ref.c, OpenMP) on a bounded sample of the same blocks, rank 0,
 N=1 only.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps and the
+result line.  --full adds the legs that take runs of their own: the whole interior-point solve
+(ipm_solve), the CPU baseline and the residual against it (cpu_baseline, residual_vs_seq_ref).
+--dump-outputs DIR writes what the last timed step returned (dx, du, pred, feasible, and K, d where
+the gains leave the chip) as DIR/<name>.npy, so two builds can be compared output for output: the
+inputs are the same from run to run (one seed).
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G | --batch B]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU: `python bench.py --gpus N` starts N ranks itself (torch.distributed.run as a child
 process, before any GPU call in the parent, which only relays rank 0's line and exit code); under
 an external launcher (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`) the
@@ -203,6 +211,39 @@ def ipm_solve_rate(problem, N, B, rank, world, G, lo, seed=11):
 
 
 BENCH_SEED = 1234  # the global batch's seed (the same on every rank)
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much (a sample beyond it)
+
+
+def dump_outputs(out, directory, rank, world):
+    """--dump-outputs: every array of the KKTResult the timed path hands its caller, as the last
+    timed step left it, to DIR/<name>.npy (DIR/<name>.rank<r>.npy when there are several ranks):
+    float64 as computed, the int32 feasible flags as float32.  Beyond DUMP_BUDGET_BYTES in all, a
+    fixed seeded sample instead: the same sorted trajectories of every per-trajectory field
+    (generator seed 0), and of a flat tiled buffer (K, d) the same sorted elements (seed 1)."""
+    import numpy as np
+    import torch
+    fields = {k: t for k, t in out._asdict().items() if t is not None}
+    Bt = out.dx.shape[0]
+    total = sum(t.numel() * 8 for t in fields.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    traj = None
+    if frac < 1.0:
+        keep = max(1, int(Bt * frac))
+        traj = torch.as_tensor(np.sort(np.random.default_rng(0).choice(Bt, keep, replace=False)),
+                               device=out.dx.device)
+    os.makedirs(directory, exist_ok=True)
+    for k, t in fields.items():
+        if frac < 1.0:
+            if not (k in ("K", "d") and t.dim() == 1):
+                t = t[traj]
+            else:  # the tiled layout's flat gains
+                keep = max(1, int(t.numel() * frac))
+                idx = np.sort(np.random.default_rng(1).integers(0, t.numel(), keep))
+                t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        name = f"{k}.npy" if world == 1 else f"{k}.rank{rank}.npy"
+        np.save(os.path.join(directory, name), a)
 
 
 def pg():
@@ -314,13 +355,20 @@ def main():
     ap.add_argument("--slice", default=None,
                     help="r/W: solve only rank r's shard of a W-rank strong-scaling run, on one "
                          "GPU without a process group (value then counts the slice only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the end-to-end "
+                         "interior-point solve (ipm_solve) and the CPU baseline with the residual "
+                         "against it (--no-ipm / --no-cpu drop either)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--lanes", type=int, default=0)
     ap.add_argument("--layout", choices=["tiled", "natural"], default="tiled",
                     help="HBM layout of the LQ blocks (tiled = what the linearisation kernels write)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-sample", type=int, default=512)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ipm", action="store_true", help="skip the end-to-end solve line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ipm", action="store_true",
+                    help="with --full: skip the end-to-end solve line")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch every step from Python instead of replaying a HIP graph of the "
                          "K timed steps (small configs then measure the host's launch rate)")
@@ -430,6 +478,8 @@ def main():
     if pg():
         dist.barrier()
     torch.cuda.synchronize()
+    if args.dump_outputs:  # `out` is what the last timed step wrote; nothing has touched it since
+        dump_outputs(out, args.dump_outputs, rank, world)
     kern_ms = ev0.elapsed_time(ev1) / args.steps          # HIP-event time per launch (stream)
     ms = wall * 1e3 / args.steps
     rank_kern_ms = [kern_ms]
@@ -493,9 +543,9 @@ def main():
     if args.slice:
         result["config"]["slice"] = args.slice
         result["config"]["slice_trajectories"] = [lo, lo + B]
-    if not args.no_ipm:
+    if args.full and not args.no_ipm:
         result["ipm_solve"] = ipm_solve_rate(args.problem, N, B, rank, world, G, lo)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             sample = min(args.cpu_sample, B)
             result["cpu_baseline"], ref = cpu_baseline(blocks, sample, args.cpu_seconds,

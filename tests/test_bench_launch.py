@@ -64,6 +64,18 @@ def test_bench_gpus_1_is_one_process():
     assert line["n_gpus"] == 1 and line["ranks_seen"] == [0]
 
 
+def test_bench_takes_full_and_dump_outputs(tmp_path):
+    """--full and --dump-outputs DIR are options of every run (a dry run computes nothing, so it
+    writes nothing)."""
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--full",
+                        "--dump-outputs", str(tmp_path / "out")], env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    (line,) = _lines(p.stdout)
+    assert line["n_gpus"] == 1 and line["dry_run"] is True
+    assert not (tmp_path / "out").exists()
+
+
 def _dump(tmp_path, gpus, extra=(), global_batch=37):
     d = tmp_path / f"w{gpus}_{global_batch}_{len(extra)}"
     d.mkdir()

@@ -9,5 +9,5 @@ run 300 pytest_kkt.log python -u -m pytest tests/test_kkt_gpu.py -x -q --timeout
 run 200 c2.log python tools/kkt_ablate.py pendulum 100 1024 64
 run 200 c2_l32.log python tools/kkt_ablate.py pendulum 100 1024 32
 run 200 c3.log python tools/kkt_ablate.py cartpole 200 4096 32
-run 200 bench_c2.log python bench.py --problem pendulum --horizon 100 --batch 1024 --steps 100 --warmup 10 --cpu-seconds 5
+run 200 bench_c2.log python bench.py --full --problem pendulum --horizon 100 --batch 1024 --steps 100 --warmup 10 --cpu-seconds 5
 run 200 prof_c2.log rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run -- python bench.py --problem pendulum --horizon 100 --batch 1024 --steps 100 --warmup 10 --no-cpu --no-ipm

@@ -8,7 +8,8 @@ par_interior_point_optimal_control, noc/par_interior_point_newton.py:228-254) --
 limiter is named: its heaviest trajectory's serial chain (max_kkt_solves) vs the slots it fills.
 
 Usage (GPU box): python tools/slice_curve.py [--ws 1,2,4,8] [--out gpurun_out/slices.json]
-Every bench call is the driver-reproducible command `python bench.py --slice r/W --no-cpu`.
+Every bench call is the driver-reproducible command `python bench.py --full --slice r/W --no-cpu`
+(--full: the ipm_solve leg is read here).
 """
 import argparse
 import contextlib
@@ -46,7 +47,8 @@ def main():
         per = []
         for r in range(W):
             t0 = time.time()
-            line = run_bench(["--slice", f"{r}/{W}", "--no-cpu", "--steps", str(args.steps)])
+            line = run_bench(["--full", "--slice", f"{r}/{W}", "--no-cpu", "--steps",
+                              str(args.steps)])
             ip = line["ipm_solve"]
             row = {"W": W, "r": r, "trajectories": line["config"]["slice_trajectories"],
                    "kkt_kernel_ms": line["roofline"]["kernel_ms"],
