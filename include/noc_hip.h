@@ -162,8 +162,12 @@ typedef struct noc_family {
 #define NOC_WS_RESUME 2    /* flags bit (noc_ipm_solve): continue every trajectory from the state
                               held in the workspace (bp, rp, r_inc, cost, hu, gnorm, it, inner,
                               total_it, kkt_solves, x, u) at its phase -- ROLLOUT: a new barrier
-                              stage, LINEARIZE: a new Newton iteration, SOLVE: a retry on the
-                              current blocks, DONE: nothing -- instead of starting at bp0 */
+                              stage, LINEARIZE: a new Newton iteration, SOLVE: a retry at the
+                              current point, DONE: nothing -- instead of starting at bp0.  A SOLVE
+                              retry recomputes the LQ blocks from x, u: the workspace's A, B, Q, R,
+                              M are not read, so the resume may follow either driver (they hold
+                              noc_ipm_solve's compact records, or the dense / compact fields of the
+                              launch-per-phase entry points) */
 #define NOC_WS_NO_REPEAT_SKIP 4 /* flags bit: recompute every retry of the par inner loop, even the
                               repeats at the rp clip that the solvers otherwise account without
                               recomputing (ws->repeats; same results bit for bit either way) */
@@ -221,6 +225,47 @@ int noc_ipm_rollout(const noc_family* fam, const noc_ipm_ws* ws, void* stream);
 int noc_ipm_step_main(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
                       void* stream);
 int noc_ipm_promote(const noc_ipm_ws* ws, void* stream);
+
+/* ---- compact (structure-aware) LQ blocks ------------------------------------------------------
+ * For the built-in generated families most entries of a stage's A, B, Q, R, M are the same for
+ * every iterate (literals, dt, the cost weights); the compact form of a field is the tiled layout
+ * above with E = the number of its entries that vary (noc_compact_width; cart-pole: A 4, B 2, Q 3,
+ * R 1, M 1 -- 12 doubles per stage with r against 36).  A field of width 0 is never read or written
+ * (pass any valid pointer).  The consumers rebuild the constants where they read a block, so every
+ * result equals the dense layout's bit for bit.  r, P and all outputs are as in the dense calls. */
+#define NOC_FIELD_A 0
+#define NOC_FIELD_B 1
+#define NOC_FIELD_Q 2
+#define NOC_FIELD_R 3
+#define NOC_FIELD_M 4
+/* 1 if the compact entry points below cover (family, lanes): pendulum and cart-pole, lanes 8, 16,
+ * 32 or 64 (not the linear family, a family registered at run time, two-wave segments or the
+ * group solve). */
+int noc_kkt_compact_supported(const noc_family* fam, int N, int lanes);
+/* doubles per stage of the compact field NOC_FIELD_*; -1 for an unsupported family or field. */
+int noc_compact_width(const noc_family* fam, int field);
+/* noc_kkt_solve_tiled (no q, c, p) on compact A, Bm, Q, R, M: same outputs, same layouts. */
+int noc_kkt_solve_compact(const noc_family* fam, int N, int B, int lanes,
+                          const double* A, const double* Bm, const double* Q, const double* R,
+                          const double* M, const double* r, const double* P, const double* x0,
+                          const double* reg, const int* active,
+                          double* dx, double* du, double* pred, int* feasible,
+                          double* K, double* d, double* S, double* v, void* stream);
+/* dense tiled A, Bm, Q (packed), R (packed), M <- the compact cA .. cM (same lanes). */
+int noc_blocks_expand(const noc_family* fam, int N, int B, int lanes,
+                      const double* cA, const double* cB, const double* cQ, const double* cR,
+                      const double* cM, double* A, double* Bm, double* Q, double* R, double* M,
+                      void* stream);
+/* noc_ipm_prepare / noc_ipm_step / noc_ipm_step_main on a workspace whose A, B, Q, R, M are the
+ * compact fields (noc_compact_width doubles per stage; noc_kkt_compact_supported(fam, ws->N,
+ * ws->lanes) must be 1): the linearisation writes, and the costate sweep and the KKT scan read, a
+ * third of the block bytes.  Every other field and every result as the dense entry points. */
+int noc_ipm_prepare_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                            void* stream);
+int noc_ipm_step_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                         int lanes, void* stream);
+int noc_ipm_step_main_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                              void* stream);
 
 /* Persistent solve: the WHOLE barrier schedule (rollout, Newton / retry loops, barrier updates)
  * of every trajectory in ONE launch, one wave64 per trajectory running its own reference control

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "../../include/noc_hip.h"
+#include "block_struct.h"
 #include "ipm_family.h"
 #include "noc_internal.h"
 #include "small_linalg.h"
@@ -76,7 +77,10 @@ __global__ __launch_bounds__(256) void promote_kernel(noc_ipm_ws w) {
 }
 
 // thread per (trajectory, chunk slot, lane) in tiled order: the A/B stores are coalesced
-template <int KIND, int NX, int NU>
+// COMPACT (here and in the costate / assemble kernels): w.A, w.B, w.Q, w.R, w.M are the compact
+// tiled fields (block_struct.h: the variable entries only, the layout noc_ipm_solve keeps there);
+// the constants are rebuilt where a block is read -- the same doubles the dense fields hold
+template <int KIND, int NX, int NU, bool COMPACT>
 __global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_ws w) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int N = w.N, L = w.lanes;
@@ -96,8 +100,18 @@ __global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_
   double fx[NX * NX], fu[NX * NU], cx[NX], cu[NU];  // all stored tiled
   f.jac(x, u, fx, fu);
   f.stage_grad(x, u, bp, cx, cu);
-  tstore_rt<NX * NX>(w.A, L, ch.cmax, b, j, l, fx);
-  tstore_rt<NX * NU>(w.B, L, ch.cmax, b, j, l, fu);
+  if constexpr (COMPACT) {
+    using BS = BlockStruct<KIND, NX, NU, true>;
+    constexpr int VA = BS::template nv<BF_A>(), VB = BS::template nv<BF_B>();
+    double va[VA > 0 ? VA : 1], vb[VB > 0 ? VB : 1];
+    BS::template compress<BF_A>(fx, va);
+    BS::template compress<BF_B>(fu, vb);
+    if constexpr (VA > 0) tstore_rt<VA>(w.A, L, ch.cmax, b, j, l, va);
+    if constexpr (VB > 0) tstore_rt<VB>(w.B, L, ch.cmax, b, j, l, vb);
+  } else {
+    tstore_rt<NX * NX>(w.A, L, ch.cmax, b, j, l, fx);
+    tstore_rt<NX * NU>(w.B, L, ch.cmax, b, j, l, fu);
+  }
   tstore_rt<NX>(w.cx, L, ch.cmax, b, j, l, cx);
   tstore_rt<NU>(w.cu, L, ch.cmax, b, j, l, cu);
   const double lc = f.stage_cost(x, u, bp);
@@ -110,7 +124,7 @@ __global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_
 // plus, per trajectory: ru_k = cu_k + B_k' lambda_{k+1} (P:34, tiled), total cost (P:142),
 // max|ru| (P:158), ||cu||_F (P:116), the regularisation fed to the KKT solve and the terminal
 // Hessian hessian(final_cost) (S:66).
-template <int KIND, int NX, int NU, int L>
+template <int KIND, int NX, int NU, int L, bool COMPACT>
 __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ipm_ws w, int mode) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = tid / L, l = tid % L;
@@ -123,6 +137,29 @@ __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ip
   const double* xN = w.x + ((size_t)b * (N + 1) + N) * NX;
   double lamN[NX];
   f.final_grad(xN, lamN);  // grad(final_cost) (C:35)
+  // a stage's A / B from the workspace (COMPACT: the stored variable entries + the constants)
+  auto load_A = [&](int jj, double* A) {
+    if constexpr (COMPACT) {
+      using BS = BlockStruct<KIND, NX, NU, true>;
+      constexpr int VA = BS::template nv<BF_A>();
+      double va[VA > 0 ? VA : 1];
+      if constexpr (VA > 0) tload_rt<VA>(w.A, L, ch.cmax, b, jj, l, va);
+      BS::template expand<BF_A>(prm, va, A);
+    } else {
+      tload_rt<NX * NX>(w.A, L, ch.cmax, b, jj, l, A);
+    }
+  };
+  auto load_B = [&](int jj, double* Bm) {
+    if constexpr (COMPACT) {
+      using BS = BlockStruct<KIND, NX, NU, true>;
+      constexpr int VB = BS::template nv<BF_B>();
+      double vb[VB > 0 ? VB : 1];
+      if constexpr (VB > 0) tload_rt<VB>(w.B, L, ch.cmax, b, jj, l, vb);
+      BS::template expand<BF_B>(prm, vb, Bm);
+    } else {
+      tload_rt<NX * NU>(w.B, L, ch.cmax, b, jj, l, Bm);
+    }
+  };
   // phases 1-2 (L > 1): chunk maps and their scan; L = 1 (grouped layout, one lane per
   // trajectory) sweeps the whole horizon from lambda_N directly
   Mat<NX, NX> G;
@@ -133,7 +170,7 @@ __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ip
     set_identity(G);
     for (int k = start + len - 1; k >= start; --k) {
       double A[NX * NX], cx[NX];
-      tload_rt<NX * NX>(w.A, L, ch.cmax, b, k - start, l, A);
+      load_A(k - start, A);
       tload_rt<NX>(w.cx, L, ch.cmax, b, k - start, l, cx);
       Mat<NX, NX> Gn;
       Vec<NX> gn;
@@ -188,8 +225,8 @@ __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ip
   double cost = 0.0, hu = 0.0, g2s = 0.0;
   for (int k = start + len - 1; k >= start; --k) {
     double A[NX * NX], Bm[NX * NU], cx[NX], cu[NU], lc, rr[NU];
-    tload_rt<NX * NX>(w.A, L, ch.cmax, b, k - start, l, A);
-    tload_rt<NX * NU>(w.B, L, ch.cmax, b, k - start, l, Bm);
+    load_A(k - start, A);
+    load_B(k - start, Bm);
     tload_rt<NX>(w.cx, L, ch.cmax, b, k - start, l, cx);
     tload_rt<NU>(w.cu, L, ch.cmax, b, k - start, l, cu);
     tload_rt<1>(w.lc, L, ch.cmax, b, k - start, l, &lc);
@@ -232,20 +269,20 @@ __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ip
   w.inner[b] = 0;
 }
 
-template <int KIND, int NX, int NU>
+template <int KIND, int NX, int NU, bool COMPACT>
 static void launch_costate(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
   const int L = w.lanes;
   const unsigned grid = (unsigned)(((long long)w.Bt * L + 63) / 64);
   switch (L) {
-    case 64: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 64>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 32: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 32>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 16: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 16>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 8: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 8>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    default: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 1>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
+    case 64: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 64, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
+    case 32: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 32, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
+    case 16: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 16, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
+    case 8: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 8, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
+    default: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 1, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
   }
 }
 
-template <int KIND, int NX, int NU>
+template <int KIND, int NX, int NU, bool COMPACT>
 __global__ __launch_bounds__(256) void assemble_kernel(noc_family prm, noc_ipm_ws w, int terminal) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int N = w.N, L = w.lanes;
@@ -273,9 +310,21 @@ __global__ __launch_bounds__(256) void assemble_kernel(noc_family prm, noc_ipm_w
     NOC_UNROLL for (int jj = i; jj < NX; ++jj) Qs(i, jj) = (i == jj) ? Q[i * NX + i] : 0.5 * (Q[i * NX + jj] + Q[jj * NX + i]);
   NOC_UNROLL for (int i = 0; i < NU; ++i)
     NOC_UNROLL for (int jj = i; jj < NU; ++jj) Rs(i, jj) = (i == jj) ? R[i * NU + i] : 0.5 * (R[i * NU + jj] + R[jj * NU + i]);
-  tstore_rt<Sym<NX>::SZ>(w.Q, L, ch.cmax, b, j, l, Qs.v);
-  tstore_rt<Sym<NU>::SZ>(w.R, L, ch.cmax, b, j, l, Rs.v);
-  tstore_rt<NX * NU>(w.M, L, ch.cmax, b, j, l, M);
+  if constexpr (COMPACT) {
+    using BS = BlockStruct<KIND, NX, NU, true>;
+    constexpr int VQ = BS::template nv<BF_Q>(), VR = BS::template nv<BF_R>(), VM = BS::template nv<BF_M>();
+    double vq[VQ > 0 ? VQ : 1], vr[VR > 0 ? VR : 1], vm[VM > 0 ? VM : 1];
+    BS::template compress<BF_Q>(Qs.v, vq);
+    BS::template compress<BF_R>(Rs.v, vr);
+    BS::template compress<BF_M>(M, vm);
+    if constexpr (VQ > 0) tstore_rt<VQ>(w.Q, L, ch.cmax, b, j, l, vq);
+    if constexpr (VR > 0) tstore_rt<VR>(w.R, L, ch.cmax, b, j, l, vr);
+    if constexpr (VM > 0) tstore_rt<VM>(w.M, L, ch.cmax, b, j, l, vm);
+  } else {
+    tstore_rt<Sym<NX>::SZ>(w.Q, L, ch.cmax, b, j, l, Qs.v);
+    tstore_rt<Sym<NU>::SZ>(w.R, L, ch.cmax, b, j, l, Rs.v);
+    tstore_rt<NX * NU>(w.M, L, ch.cmax, b, j, l, M);
+  }
   if (terminal == NOC_TERMINAL_STAGE0 && k == 0) gstore<NX * NX>(w.P + (size_t)b * NX * NX, Q);  // P:73
 }
 
@@ -415,26 +464,34 @@ static hipError_t rollout_t(const noc_family& p, const noc_ipm_ws& w, hipStream_
 }
 
 // linearise + costates + LQ blocks for phase-LINEARIZE trajectories, then LINEARIZE -> SOLVE
-template <int KIND, int NX, int NU>
-static hipError_t prepare_main_t(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
+template <int KIND, int NX, int NU, bool COMPACT>
+static hipError_t prepare_main_c(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
                                  hipStream_t s) {
   const int bt_grid = (w.Bt + 255) / 256;
   const long long cmax = (w.N + w.lanes - 1) / w.lanes;
   const unsigned st_grid = (unsigned)(((long long)w.Bt * cmax * w.lanes + 255) / 256);
-  hipLaunchKernelGGL((linearize_kernel<KIND, NX, NU>), dim3(st_grid), dim3(256), 0, s, p, w);
-  launch_costate<KIND, NX, NU>(p, w, mode, s);
-  hipLaunchKernelGGL((assemble_kernel<KIND, NX, NU>), dim3(st_grid), dim3(256), 0, s, p, w, terminal);
+  hipLaunchKernelGGL((linearize_kernel<KIND, NX, NU, COMPACT>), dim3(st_grid), dim3(256), 0, s, p, w);
+  launch_costate<KIND, NX, NU, COMPACT>(p, w, mode, s);
+  hipLaunchKernelGGL((assemble_kernel<KIND, NX, NU, COMPACT>), dim3(st_grid), dim3(256), 0, s, p, w, terminal);
   hipLaunchKernelGGL(mark_solve_kernel, dim3(bt_grid), dim3(256), 0, s, w);
   return hipGetLastError();
 }
 
+// compact: the workspace's block fields are the compact ones (the _compact entry points)
+template <int KIND, int NX, int NU>
+static hipError_t prepare_main_t(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
+                                 bool compact, hipStream_t s) {
+  return compact ? prepare_main_c<KIND, NX, NU, true>(p, w, mode, terminal, s)
+                 : prepare_main_c<KIND, NX, NU, false>(p, w, mode, terminal, s);
+}
+
 template <int KIND, int NX, int NU>
 static hipError_t prepare_t(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                            hipStream_t s) {
+                            bool compact, hipStream_t s) {
   hipError_t e = rollout_t<KIND, NX, NU>(p, w, s, 1);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
-  return prepare_main_t<KIND, NX, NU>(p, w, mode, terminal, s);
+  return prepare_main_t<KIND, NX, NU>(p, w, mode, terminal, compact, s);
 }
 
 template <int KIND, int NX, int NU>
@@ -446,9 +503,9 @@ static hipError_t trial_t(const noc_family& p, const noc_ipm_ws& w, int mode, hi
 
 // family dispatch: one instantiation per NOC_FAMILY line of families.def
 hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                       hipStream_t s) {
+                       bool compact, hipStream_t s) {
 #define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return prepare_t<K, X, U>(p, w, mode, terminal, s);
+  if (p.kind == K && p.nx == X && p.nu == U) return prepare_t<K, X, U>(p, w, mode, terminal, compact, s);
 #include NOC_FAMILIES_DEF
 #undef NOC_FAMILY
   return hipErrorInvalidValue;
@@ -463,9 +520,9 @@ hipError_t ipm_rollout(const noc_family& p, const noc_ipm_ws& w, hipStream_t s) 
 }
 
 hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                            hipStream_t s) {
+                            bool compact, hipStream_t s) {
 #define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return prepare_main_t<K, X, U>(p, w, mode, terminal, s);
+  if (p.kind == K && p.nx == X && p.nu == U) return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
 #include NOC_FAMILIES_DEF
 #undef NOC_FAMILY
   return hipErrorInvalidValue;

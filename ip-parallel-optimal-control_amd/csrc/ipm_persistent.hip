@@ -21,6 +21,7 @@
 #include "../../include/noc_hip.h"
 #include "block_struct.h"
 #include "ipm_family.h"
+#include "kkt_compact_src.h"
 #include "kkt_scan_impl.h"
 #include "noc_internal.h"
 
@@ -84,54 +85,6 @@ template <int NX, int NU>
 __host__ __device__ constexpr int xlds_off(int N, int spec = 1, int wv = 0) {
   return spec * (slot_doubles<NX, NU>(N) + state_doubles()) + specio_doubles(spec) + wv * xlds_doubles<NX, NU>(N);
 }
-
-// The KKT scan's block source in the persistent solver: the workspace's compact tiled fields (only
-// the variable entries of A, B, Q, R, M; block_struct.h), expanded with the family's constants as
-// they are loaded.  BS = BlockStruct<..., false> is the dense layout (the NOC_PERSIST_STRUCT=0
-// instance), which loads exactly what ArgsSrc does.
-template <class BS, int NX, int NU, int L>
-struct CompactSrc {
-  using Struct = BS;
-  const KKTArgs& a;
-  const noc_family& p;
-  int traj, l, cmax;
-  size_t tN;
-  template <int F, bool LAST = false>
-  NOC_DEV void field(const double* base, int j, double* full) const {
-    constexpr int EV = BS::template nv<F>();
-    double v[EV > 0 ? EV : 1];
-    if constexpr (EV > 0) tload_pol<EV, L, LAST>(base, traj, j, l, cmax, v);
-    BS::template expand<F>(p, v, full);
-  }
-  // PART / LAST: as load_stage (kkt_scan_impl.h)
-  template <int PART, bool LAST = false>
-  NOC_DEV void stage_part(int s, int j, double reg, StageData<NX, NU>& st) const {
-    constexpr bool REST = PART != 2, WQ = PART != 1, WAB = REST && PART != 3;
-    (void)s;
-    (void)reg;
-    if constexpr (WAB) {
-      field<BF_A>(a.A, j, st.A.v);
-      field<BF_B>(a.Bm, j, st.B.v);
-    }
-    if constexpr (WQ) field<BF_Q, LAST>(a.Q, j, st.Q.v);
-    if constexpr (REST) {
-      field<BF_R, LAST>(a.R, j, st.R.v);
-      field<BF_M, LAST>(a.M, j, st.M.v);
-      tload_pol<NU, L, LAST>(a.r, traj, j, l, cmax, st.r.v);
-    }
-  }
-  NOC_DEV void stage(int s, int j, double reg, StageData<NX, NU>& st) const { stage_part<0>(s, j, reg, st); }
-  NOC_DEV void stage_last(int s, int j, double reg, StageData<NX, NU>& st) const {
-    stage_part<0, true>(s, j, reg, st);
-  }
-  NOC_DEV void ab(int s, int j, Mat<NX, NX>& A, Mat<NX, NU>& Bm, Vec<NX>& c) const {
-    (void)s;
-    field<BF_A, true>(a.A, j, A.v);  // phase 4: the last read of A, B (non-temporal)
-    field<BF_B, true>(a.Bm, j, Bm.v);
-    set_zero(c);
-  }
-  NOC_DEV void cvec(int, int, Vec<NX>& c) const { set_zero(c); }
-};
 
 }  // namespace
 

@@ -1,0 +1,6 @@
+// Instantiation unit of the compact KKT scan (kkt_compact_src.h): cart-pole (4, 1), lanes 64.
+#include "kkt_compact_src.h"
+
+namespace noc {
+template hipError_t launch_kkt_compact<NOC_FAMILY_CARTPOLE, 4, 1, 64>(const noc_family&, const KKTArgs&, hipStream_t);
+}  // namespace noc

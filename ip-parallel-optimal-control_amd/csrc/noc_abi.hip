@@ -209,6 +209,76 @@ int noc_kkt_solve_tiled(int nx, int nu, int N, int B, int lanes, const double* A
                     reg, active, dx, du, pred, feasible, K, d, S, v, stream);
 }
 
+int noc_kkt_compact_supported(const noc_family* fam, int N, int lanes) {
+  return (fam && N >= 1 && noc::kkt_compact_supported(*fam, lanes)) ? 1 : 0;
+}
+
+int noc_compact_width(const noc_family* fam, int field) {
+  if (!fam) return fail(-1, "family is NULL");
+  const int w = noc::compact_width(*fam, field);
+  return w < 0 ? fail(-1, "noc_compact_width: unsupported family or field") : w;
+}
+
+// family / dims / lanes of the compact entry points (before any HIP call)
+static int check_compact_dims(const noc_family* fam, int N, int B, int lanes) {
+  if (!fam) return fail(-1, "family is NULL");
+  if (N < 1) return fail(-1, "horizon N must be >= 1");
+  if (B < 0) return fail(-1, "batch B must be >= 0");
+  if (!noc::kkt_compact_supported(*fam, lanes))
+    return fail(-1, "compact blocks: unsupported family or lanes (" + std::to_string(lanes) +
+                        "); pendulum and cart-pole at lanes 8, 16, 32 or 64 (noc_kkt_compact_supported)");
+  return 0;
+}
+
+int noc_kkt_solve_compact(const noc_family* fam, int N, int B, int lanes, const double* A,
+                          const double* Bm, const double* Q, const double* R, const double* M,
+                          const double* r, const double* P, const double* x0, const double* reg,
+                          const int* active, double* dx, double* du, double* pred, int* feasible,
+                          double* K, double* d, double* S, double* v, void* stream) {
+  if (check_compact_dims(fam, N, B, lanes)) return -1;
+  const void* req[] = {A, Bm, Q, R, M, r, P};
+  const char* names[] = {"A", "B", "Q", "R", "M", "r", "P"};
+  for (int i = 0; i < 7; ++i)
+    if (check_ptr(req[i], names[i], true)) return -1;
+  if (check_ptr(x0, "x0", false) || check_ptr(K, "K", false) || check_ptr(d, "d", false) ||
+      check_ptr(S, "S", false) || check_ptr(v, "v", false) || check_ptr(dx, "dx", false) ||
+      check_ptr(du, "du", false) || check_ptr(reg, "reg", false, 8) ||
+      check_ptr(pred, "pred", false, 8) || check_ptr(feasible, "feasible", false, 4) ||
+      check_ptr(active, "active", false, 4))
+    return -1;
+  if (B == 0) return 0;
+  const int nx = fam->nx, nu = fam->nu;
+  const bool on_chip = (dx || du) && noc::kkt_lds_bytes_rt(nx, nu, N, lanes) > 0;
+  if ((!K || !d) && !on_chip) {
+    fail(-2, "K and d are required (workspace) unless noc_kkt_gains_on_chip() is 1");
+    return -1;
+  }
+  noc::KKTArgs a{};
+  a.N = N;
+  a.B = B;
+  a.mode = noc::MODE_FULL;
+  a.A = A; a.Bm = Bm; a.Q = Q; a.R = R; a.M = M; a.r = r;
+  a.P = P; a.x0 = x0; a.reg = reg; a.active = active;
+  a.dx = dx; a.du = du; a.pred = pred; a.K = K; a.d = d; a.S = S; a.v = v;
+  a.feasible = feasible;
+  a.ablate = g_ablate;
+  a.tiled = 1;
+  return hip_status(noc::kkt_compact_dispatch(*fam, a, lanes, static_cast<hipStream_t>(stream)),
+                    "kkt_scan_compact launch");
+}
+
+int noc_blocks_expand(const noc_family* fam, int N, int B, int lanes, const double* cA,
+                      const double* cB, const double* cQ, const double* cR, const double* cM,
+                      double* A, double* Bm, double* Q, double* R, double* M, void* stream) {
+  if (check_compact_dims(fam, N, B, lanes)) return -1;
+  const void* req[] = {cA, cB, cQ, cR, cM, A, Bm, Q, R, M};
+  for (const void* p : req)
+    if (check_ptr(p, "blocks_expand argument", true)) return -1;
+  if (B == 0) return 0;
+  const noc::ExpandArgs e{N, B, lanes, cA, cB, cQ, cR, cM, A, Bm, Q, R, M};
+  return hip_status(noc::blocks_expand(*fam, e, static_cast<hipStream_t>(stream)), "blocks_expand");
+}
+
 long long noc_tiled_doubles(int N, int B, int lanes, int E) {
   if (N < 1 || B < 0 || lanes < 1 || E < 1) return -1;
   if (lanes == 1)  // grouped layout: whole records of GROUP_T trajectories
@@ -280,17 +350,36 @@ int noc_ipm_init(const noc_ipm_ws* ws, double bp0, void* stream) {
   return hip_status(noc::ipm_init(*ws, bp0, static_cast<hipStream_t>(stream)), "ipm_init");
 }
 
-int noc_ipm_prepare(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
-                    void* stream) {
+// the compact twins' extra check: the workspace's block fields can be compact for (family, lanes)
+static int check_compact(const noc_family* fam, const noc_ipm_ws* ws) {
+  if (!noc::kkt_compact_supported(*fam, ws->lanes))
+    return fail(-1, "compact blocks: unsupported family or workspace lanes (noc_kkt_compact_supported)");
+  return 0;
+}
+
+static int ipm_prepare_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                           bool compact, void* stream) {
   if (!fam) return fail(-2, "family is NULL");
   int rc = check_ipm(fam, ws);
   if (rc) return rc;
+  if (compact && (rc = check_compact(fam, ws))) return rc;
   if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
   if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
     return fail(-1, "bad terminal option");
   if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_prepare(*fam, *ws, mode, terminal, static_cast<hipStream_t>(stream)),
+  return hip_status(noc::ipm_prepare(*fam, *ws, mode, terminal, compact, static_cast<hipStream_t>(stream)),
                     "ipm_prepare");
+}
+
+int noc_ipm_prepare(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                    void* stream) {
+  return ipm_prepare_any(fam, ws, mode, terminal, false, stream);
+}
+
+int noc_ipm_prepare_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                            void* stream) {
+  if (!fam || !ws) return fail(-1, "noc_ipm_prepare_compact: family or workspace is NULL");
+  return ipm_prepare_any(fam, ws, mode, terminal, true, stream);
 }
 
 int noc_ipm_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, void* stream) {
@@ -316,17 +405,29 @@ int noc_total_cost(const noc_family* fam, int N, int B, const double* x, const d
                     "total_cost");
 }
 
-static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, void* stream);
+static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, bool compact,
+                         void* stream);
 
-int noc_ipm_step(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, int lanes,
-                 void* stream) {
+static int ipm_step_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                        int lanes, bool compact, void* stream) {
   // lanes: 0 = the workspace's; any other value must equal it (the blocks are laid out for it)
   if (ws && lanes != 0 && lanes != ws->lanes)
     return fail(-1, "noc_ipm_step: lanes (" + std::to_string(lanes) + ") differs from the workspace's (" +
                         std::to_string(ws->lanes) + "); pass 0 or ws->lanes");
-  int rc = noc_ipm_prepare(fam, ws, mode, terminal, stream);
+  int rc = ipm_prepare_any(fam, ws, mode, terminal, compact, stream);
   if (rc) return rc;
-  return kkt_and_trial(fam, ws, mode, stream);
+  return kkt_and_trial(fam, ws, mode, compact, stream);
+}
+
+int noc_ipm_step(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, int lanes,
+                 void* stream) {
+  return ipm_step_any(fam, ws, mode, terminal, lanes, false, stream);
+}
+
+int noc_ipm_step_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                         int lanes, void* stream) {
+  if (!fam || !ws) return fail(-1, "noc_ipm_step_compact: family or workspace is NULL");
+  return ipm_step_any(fam, ws, mode, terminal, lanes, true, stream);
 }
 
 int noc_ipm_rollout(const noc_family* fam, const noc_ipm_ws* ws, void* stream) {
@@ -344,19 +445,31 @@ int noc_ipm_promote(const noc_ipm_ws* ws, void* stream) {
   return hip_status(noc::ipm_promote(*ws, static_cast<hipStream_t>(stream)), "ipm_promote");
 }
 
-int noc_ipm_step_main(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
-                      void* stream) {
+static int ipm_step_main_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                             bool compact, void* stream) {
   if (!fam) return fail(-2, "family is NULL");
   int rc = check_ipm(fam, ws);
   if (rc) return rc;
+  if (compact && (rc = check_compact(fam, ws))) return rc;
   if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
   if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
     return fail(-1, "bad terminal option");
   if (ws->Bt == 0) return 0;
-  rc = hip_status(noc::ipm_prepare_main(*fam, *ws, mode, terminal, static_cast<hipStream_t>(stream)),
-                  "ipm_prepare_main");
+  rc = hip_status(noc::ipm_prepare_main(*fam, *ws, mode, terminal, compact,
+                                        static_cast<hipStream_t>(stream)), "ipm_prepare_main");
   if (rc) return rc;
-  return kkt_and_trial(fam, ws, mode, stream);
+  return kkt_and_trial(fam, ws, mode, compact, stream);
+}
+
+int noc_ipm_step_main(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                      void* stream) {
+  return ipm_step_main_any(fam, ws, mode, terminal, false, stream);
+}
+
+int noc_ipm_step_main_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                              void* stream) {
+  if (!fam || !ws) return fail(-1, "noc_ipm_step_main_compact: family or workspace is NULL");
+  return ipm_step_main_any(fam, ws, mode, terminal, true, stream);
 }
 
 int noc_debug_phase_cycles(long long* out, int n, int reset) {
@@ -552,9 +665,18 @@ int noc_check_feasibility(const noc_family* fam, int N, int B, const double* x, 
                                           static_cast<hipStream_t>(stream)), "check_feasibility");
 }
 
-static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, void* stream) {
+static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, bool compact,
+                         void* stream) {
   // the trial step needs dx, du only: gains stay on chip when they fit (ws->K, ws->d otherwise)
   const bool on_chip = noc_kkt_gains_on_chip(fam->nx, fam->nu, ws->N, ws->lanes) == 1;
+  if (compact) {
+    int rc = noc_kkt_solve_compact(fam, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q, ws->R, ws->M,
+                                   ws->r, ws->P, nullptr, ws->reg, ws->kkt_active, ws->dx, ws->du,
+                                   ws->pred, ws->feasible, on_chip ? nullptr : ws->K,
+                                   on_chip ? nullptr : ws->d, nullptr, nullptr, stream);
+    if (rc) return rc;
+    return noc_ipm_trial(fam, ws, mode, stream);
+  }
   int rc = noc_kkt_solve_tiled(fam->nx, fam->nu, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q,
                                ws->R, ws->M, ws->r, nullptr, nullptr, ws->P, nullptr, nullptr,
                                ws->reg, ws->kkt_active, ws->dx, ws->du, ws->pred, ws->feasible,

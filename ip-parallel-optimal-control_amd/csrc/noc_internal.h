@@ -207,15 +207,28 @@ hipError_t kkt_group_dispatch(int nx, int nu, const KKTArgs& a, hipStream_t stre
 template <int NX, int NU>
 hipError_t kkt_dispatch_shape(const KKTArgs& a, int lanes, hipStream_t stream);
 bool kkt_supported(int nx, int nu);
+// the stand-alone scan on compact blocks (kkt_compact.hip; kernels: kkt_compact_src.h): built-in
+// generated families, one-wave segments.  field: BF_A .. BF_M (block_struct.h)
+bool kkt_compact_supported(const noc_family& p, int lanes);
+int compact_width(const noc_family& p, int field);
+hipError_t kkt_compact_dispatch(const noc_family& p, const KKTArgs& a, int lanes, hipStream_t stream);
+// dense tiled A, B, Q, R, M <- the compact fields + the family's constants
+struct ExpandArgs {
+  int N, B, lanes;
+  const double *cA, *cB, *cQ, *cR, *cM;
+  double *A, *Bm, *Q, *R, *M;
+};
+hipError_t blocks_expand(const noc_family& p, const ExpandArgs& e, hipStream_t stream);
 int kkt_default_lanes(int nx, int nu, int N);
 int kkt_pick_lanes(int nx, int nu, int N, int B);
 
+// compact: w.A, w.B, w.Q, w.R, w.M are the compact tiled fields (block_struct.h)
 hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                       hipStream_t s);
+                       bool compact, hipStream_t s);
 hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s);
 hipError_t ipm_rollout(const noc_family& p, const noc_ipm_ws& w, hipStream_t s);
 hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                            hipStream_t s);
+                            bool compact, hipStream_t s);
 hipError_t ipm_promote(const noc_ipm_ws& w, hipStream_t s);
 hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s);
 // persistent whole-solve kernel (ipm_persistent.hip)

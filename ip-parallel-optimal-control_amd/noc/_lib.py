@@ -21,7 +21,12 @@ KKT_KERNEL_SOURCES = {
     "kkt_scan": ("csrc/kkt_scan_impl.h", "csrc/kkt_scan_2x1.hip", "csrc/kkt_scan_4x1.hip",
                  "csrc/kkt_scan_4x1_l32.hip", "csrc/kkt_scan_4x1_l32nt.hip",
                  "csrc/kkt_scan_4x1_l128.hip", "csrc/kkt_scan_8x4.hip", "csrc/kkt_scan_8x4_l32.hip",
-                 "csrc/kkt_scan_8x4_l16.hip", "csrc/kkt_scan_8x4_l8.hip") + _COMMON_SOURCES,
+                 "csrc/kkt_scan_8x4_l16.hip", "csrc/kkt_scan_8x4_l8.hip",
+                 # the compact scan (the built-in generated families' bench launches run it)
+                 "csrc/kkt_compact_src.h", "csrc/block_struct.h", "csrc/kkt_compact.hip",
+                 "csrc/kkt_scan_compact_pendulum.hip", "csrc/kkt_scan_compact_cartpole_l8.hip",
+                 "csrc/kkt_scan_compact_cartpole_l16.hip", "csrc/kkt_scan_compact_cartpole_l32.hip",
+                 "csrc/kkt_scan_compact_cartpole_l64.hip") + _COMMON_SOURCES,
     "kkt_group8": ("csrc/kkt_group_impl.h", "csrc/kkt_group8_impl.h", "csrc/kkt_group.hip")
     + _COMMON_SOURCES,
 }
@@ -75,6 +80,7 @@ WS_INT_FIELDS = ["feasible", "phase", "kkt_active", "it", "inner", "total_it", "
 WS_STATE_FIELDS = ["bp", "rp", "rinc", "cost", "hu", "gnorm", "reg"]
 
 
+FIELD_A, FIELD_B, FIELD_Q, FIELD_R, FIELD_M = range(5)  # NOC_FIELD_* (noc_compact_width)
 WS_OPT_FIELDS = ["order"]  # optional pointers, NULL unless set (noc_ipm_ws.order)
 
 
@@ -96,6 +102,13 @@ SIGNATURES.update({
     "noc_ipm_rollout": (_i, [_fp, _wp, _dp]),
     "noc_ipm_step_main": (_i, [_fp, _wp, _i, _i, _dp]),
     "noc_ipm_promote": (_i, [_wp, _dp]),
+    "noc_kkt_compact_supported": (_i, [_fp, _i, _i]),
+    "noc_compact_width": (_i, [_fp, _i]),
+    "noc_kkt_solve_compact": (_i, [_fp, _i, _i, _i] + [_dp] * 10 + [_dp] * 8 + [_dp]),
+    "noc_blocks_expand": (_i, [_fp, _i, _i, _i] + [_dp] * 10 + [_dp]),
+    "noc_ipm_prepare_compact": (_i, [_fp, _wp, _i, _i, _dp]),
+    "noc_ipm_step_compact": (_i, [_fp, _wp, _i, _i, _i, _dp]),
+    "noc_ipm_step_main_compact": (_i, [_fp, _wp, _i, _i, _dp]),
     "noc_ipm_solve_supported": (_i, [_fp, _i, _i]),
     "noc_debug_phase_cycles": (_i, [ctypes.POINTER(ctypes.c_longlong), _i, _i]),
     "noc_debug_traj_times": (_i, [ctypes.POINTER(ctypes.c_longlong), _i]),

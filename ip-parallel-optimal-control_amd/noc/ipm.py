@@ -46,9 +46,15 @@ def carve_zeros(spec, device, dtype, align_bytes: int = 256):
 
 class BatchedIPM:
     def __init__(self, family, N: int, batch: int, device="cuda", lanes: int = 0,
-                 overlap: Optional[bool] = None, persistent: bool = False):
+                 overlap: Optional[bool] = None, persistent: bool = False,
+                 compact: Optional[bool] = None):
         """persistent=True: solve() runs the whole barrier schedule in one launch
-        (noc_ipm_solve, one wave per trajectory; forces lanes = 64)."""
+        (noc_ipm_solve, one wave per trajectory; forces lanes = 64).
+        compact: the launch-per-phase engine keeps only the variable entries of A, B, Q, R, M in
+        its workspace (the compact fields of include/noc_hip.h: a third of the block bytes for
+        cart-pole; same results bit for bit).  None = wherever the library supports it
+        (noc_kkt_compact_supported: pendulum / cart-pole, lanes 8-64); NOC_KKT_COMPACT=0 turns
+        the automatic choice off.  Persistent engines manage their own blocks."""
         if not torch.cuda.is_available():
             raise _lib.NocError("no HIP device visible: the MI355X path has no CPU fallback")
         self.family = family
@@ -70,15 +76,27 @@ class BatchedIPM:
         self.lanes = lanes or lib.noc_kkt_default_lanes(family.nx, family.nu, N)
         if not lib.noc_family_supported(ctypes.byref(self.fam_c)):
             raise _lib.NocError(f"unsupported family kind={family.kind} nx={family.nx} nu={family.nu}")
+        can_compact = (not self.persistent and lib.noc_kkt_compact_supported(
+            ctypes.byref(self.fam_c), int(N), int(self.lanes)) == 1)
+        if compact is None:
+            compact = can_compact and os.environ.get("NOC_KKT_COMPACT") != "0"
+        elif compact and not can_compact:
+            raise _lib.NocError("compact blocks need a non-persistent engine of a supported family "
+                                "and lanes (noc_kkt_compact_supported)")
+        self.compact = bool(compact)
         Bt, N, nx, nu = self.Bt, self.N, self.nx, self.nu
         f64 = dict(device=self.device, dtype=torch.float64)
         i32 = dict(device=self.device, dtype=torch.int32)
         L = self.lanes
         tiled = lambda E: (int(lib.noc_tiled_doubles(N, Bt, L, E)),)
         # LQ blocks and gains in the KKT scan's tiled layout (Q, R packed symmetric)
-        shapes = dict(x=(Bt, N + 1, nx), u=(Bt, N, nu), x0=(Bt, nx), A=tiled(nx * nx),
-                      B=tiled(nx * nu), Q=tiled(nx * (nx + 1) // 2), R=tiled(nu * (nu + 1) // 2),
-                      M=tiled(nx * nu), r=tiled(nu), P=(Bt, nx, nx), cx=tiled(nx),
+        widths = dict(A=nx * nx, B=nx * nu, Q=nx * (nx + 1) // 2, R=nu * (nu + 1) // 2, M=nx * nu)
+        if self.compact:  # a field without variable entries is never touched: one double per stage
+            widths = {k: max(1, int(lib.noc_compact_width(ctypes.byref(self.fam_c), f)))
+                      for k, f in zip("ABQRM", range(5))}
+        shapes = dict(x=(Bt, N + 1, nx), u=(Bt, N, nu), x0=(Bt, nx), A=tiled(widths["A"]),
+                      B=tiled(widths["B"]), Q=tiled(widths["Q"]), R=tiled(widths["R"]),
+                      M=tiled(widths["M"]), r=tiled(nu), P=(Bt, nx, nx), cx=tiled(nx),
                       cu=tiled(nu), lc=tiled(1), lam=(Bt, N + 1, nx), dx=(Bt, N + 1, nx),
                       du=(Bt, N, nu), pred=(Bt,), K=tiled(nu * nx), d=tiled(nu))
         for k in _lib.WS_STATE_FIELDS:
@@ -122,16 +140,17 @@ class BatchedIPM:
             self.ev_main.record(torch.cuda.current_stream(self.device))
 
     def prepare(self, mode: int, terminal: int):
-        _lib.check(self._lib.noc_ipm_prepare(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode,
-                                             terminal, self._stream()), "noc_ipm_prepare", self._lib)
+        fn = self._lib.noc_ipm_prepare_compact if self.compact else self._lib.noc_ipm_prepare
+        _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
+                      self._stream()), "noc_ipm_prepare", self._lib)
 
     def step(self, mode: int, terminal: int):
         """One device iteration.  With overlap (default) the rollouts of trajectories that start
         a barrier stage run on a second stream beside the other trajectories' Newton step."""
         if not self.overlap:
-            _lib.check(self._lib.noc_ipm_step(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
-                                              mode, terminal, self.lanes, self._stream()),
-                       "noc_ipm_step", self._lib)
+            fn = self._lib.noc_ipm_step_compact if self.compact else self._lib.noc_ipm_step
+            _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
+                          self.lanes, self._stream()), "noc_ipm_step", self._lib)
             return
         main = torch.cuda.current_stream(self.device)
         roll = self.roll_stream
@@ -139,9 +158,9 @@ class BatchedIPM:
         _lib.check(self._lib.noc_ipm_rollout(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
                                              roll.cuda_stream), "noc_ipm_rollout", self._lib)
         self.ev_roll.record(roll)
-        _lib.check(self._lib.noc_ipm_step_main(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
-                                               mode, terminal, main.cuda_stream),
-                   "noc_ipm_step_main", self._lib)
+        fn = self._lib.noc_ipm_step_main_compact if self.compact else self._lib.noc_ipm_step_main
+        _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
+                      main.cuda_stream), "noc_ipm_step_main", self._lib)
         main.wait_event(self.ev_roll)
         _lib.check(self._lib.noc_ipm_promote(ctypes.byref(self.ws), main.cuda_stream),
                    "noc_ipm_promote", self._lib)
@@ -330,8 +349,13 @@ class BatchedIPM:
         return int(self.t["kkt_solves"].max().item()) if self.Bt else 0
 
     def tiled_blocks(self):
-        from .lqt import TiledBlocks
+        """The workspace's LQ blocks for lqt.kkt_solve_tiled: TiledBlocks, or CompactBlocks of a
+        compact engine."""
+        from .lqt import CompactBlocks, TiledBlocks
         t = self.t
+        if self.compact:
+            return CompactBlocks(t["A"], t["B"], t["Q"], t["R"], t["M"], t["r"], t["P"], self.nx,
+                                 self.nu, self.N, self.Bt, self.lanes, self.family, self.fam_c)
         return TiledBlocks(t["A"], t["B"], t["Q"], t["R"], t["M"], t["r"], t["P"], self.nx,
                            self.nu, self.N, self.Bt, self.lanes)
 
@@ -339,6 +363,16 @@ class BatchedIPM:
         """The LQ blocks relaid out to the natural (Bt, N, ...) layout (tests / export)."""
         from .lqt import untile
         Bt, N, nx, nu, L, t = self.Bt, self.N, self.nx, self.nu, self.lanes, self.t
+        if self.compact:  # dense tiled copies of the compact fields (noc_blocks_expand)
+            from .lqt import tiled_numel
+            dense = {k: torch.empty(tiled_numel(N, Bt, L, E), device=self.device, dtype=torch.float64)
+                     for k, E in dict(A=nx * nx, B=nx * nu, Q=nx * (nx + 1) // 2,
+                                      R=nu * (nu + 1) // 2, M=nx * nu).items()}
+            _lib.check(self._lib.noc_blocks_expand(
+                ctypes.byref(self.fam_c), N, Bt, L, *(self.t[k].data_ptr() for k in "ABQRM"),
+                *(dense[k].data_ptr() for k in "ABQRM"), self._stream()), "noc_blocks_expand",
+                self._lib)
+            t = dict(t, **dense)
         return dict(A=untile(t["A"], (Bt, N, nx, nx), L), B=untile(t["B"], (Bt, N, nx, nu), L),
                     Q=untile(t["Q"], (Bt, N, nx, nx), L, sym=True),
                     R=untile(t["R"], (Bt, N, nu, nu), L, sym=True),

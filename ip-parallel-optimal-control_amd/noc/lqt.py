@@ -160,6 +160,26 @@ class TiledBlocks(NamedTuple):
     lanes: int
 
 
+class CompactBlocks(NamedTuple):
+    """TiledBlocks whose A, B, Q, R, M hold only the entries that vary from stage to stage (the
+    compact fields of include/noc_hip.h, noc_compact_width doubles per stage) of `family`'s
+    blocks; r and P as in TiledBlocks.  What a compact BatchedIPM engine's workspace holds."""
+    A: torch.Tensor
+    B: torch.Tensor
+    Q: torch.Tensor
+    R: torch.Tensor
+    M: torch.Tensor
+    r: torch.Tensor
+    P: torch.Tensor        # natural (Bt, nx, nx)
+    nx: int
+    nu: int
+    N: int
+    Bt: int
+    lanes: int
+    family: object         # noc.problems.Family
+    fam_c: object          # its noc_family struct (family.to_c(), built once)
+
+
 def to_tiled(A, B, Q, R, M, r, P, lanes: int) -> TiledBlocks:
     Bt, N, nx, _ = A.shape
     nu = B.shape[-1]
@@ -168,9 +188,10 @@ def to_tiled(A, B, Q, R, M, r, P, lanes: int) -> TiledBlocks:
                        nx, nu, N, Bt, lanes)
 
 
-def kkt_solve_tiled(tb: TiledBlocks, reg=None, x0=None, active=None, want_value=False,
+def kkt_solve_tiled(tb, reg=None, x0=None, active=None, want_value=False,
                     out: Optional[KKTResult] = None, want_gains: bool = True) -> KKTResult:
-    """Fused KKT solve on tiled blocks (the layout the interior-point workspace produces).
+    """Fused KKT solve on tiled blocks (the layout the interior-point workspace produces; dense
+    TiledBlocks or CompactBlocks -- same results bit for bit).
     K, d of the result are flat tiled buffers (None if want_gains=False and they fit on chip);
     dx, du, S, v natural."""
     Bt, N, nx, nu, L = tb.Bt, tb.N, tb.nx, tb.nu, tb.lanes
@@ -187,6 +208,15 @@ def kkt_solve_tiled(tb: TiledBlocks, reg=None, x0=None, active=None, want_value=
             torch.empty(Bt, N + 1, nx, **f64) if want_value else None)
     if active is not None:
         active = active.to(device=dev, dtype=torch.int32).contiguous()
+    if isinstance(tb, CompactBlocks):
+        import ctypes
+        lib = _lib.load_for(tb.family)
+        rc = lib.noc_kkt_solve_compact(ctypes.byref(tb.fam_c), N, Bt, L, *(_lib.ptr(t) for t in (
+            tb.A, tb.B, tb.Q, tb.R, tb.M, tb.r, tb.P, _c(x0, "x0"), _c(reg, "reg"), active,
+            out.dx, out.du, out.pred, out.feasible, out.K, out.d, out.S, out.v)),
+            _lib.stream_handle(dev))
+        _lib.check(rc, "noc_kkt_solve_compact", lib)
+        return out
     lib = _lib.for_shape(nx, nu)
     rc = lib.noc_kkt_solve_tiled(nx, nu, N, Bt, L, *(_lib.ptr(t) for t in (
         tb.A, tb.B, tb.Q, tb.R, tb.M, tb.r, None, None, tb.P, None, _c(x0, "x0"), _c(reg, "reg"),
