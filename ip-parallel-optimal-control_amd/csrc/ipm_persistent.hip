@@ -803,14 +803,19 @@ static int heavy_count(const noc_ipm_ws& w, int simds, bool* spec2) {
   const char* hs = getenv("NOC_PERSIST_HEAVY_SPEC");
   *spec2 = false;
   if (!w.order || simds <= 0) return 0;
+  // the candidates exist on the structure-aware blocks only (launch_spec), and both launches of a
+  // split write the same w.A ... w.M: under NOC_PERSIST_STRUCT=0 no candidates (as spec_auto), so
+  // the heavy launch takes the dense one-wave instance like the rest, or there is no split
+  const char* senv = getenv("NOC_PERSIST_STRUCT");
+  const bool dense = senv && atoi(senv) == 0;
   int h;
   bool sp;
   if (env) {
     h = atoi(env);
-    sp = hs && atoi(hs) == 2;
+    sp = hs && atoi(hs) == 2 && !dense;
     if (w.Bt <= (sp ? simds / 2 : simds)) return 0;
   } else {
-    if ((hs && atoi(hs) == 0) || w.N > 320 || w.Bt <= simds || w.Bt > 2 * simds) return 0;
+    if (dense || (hs && atoi(hs) == 0) || w.N > 320 || w.Bt <= simds || w.Bt > 2 * simds) return 0;
     h = simds / 8;
     sp = true;
   }

@@ -261,6 +261,8 @@ class BatchedIPM:
     def _heavy_split_eligible(self) -> bool:
         if os.environ.get("NOC_PERSIST_HEAVY_SPEC") == "0" or os.environ.get("NOC_PERSIST_SPEC") == "1":
             return False
+        if os.environ.get("NOC_PERSIST_STRUCT") == "0":  # no candidates on dense blocks: no split
+            return False
         simds = self._simds()
         return (self.persistent and self.family.kind == _lib.FAMILY_CARTPOLE and self.N <= 320
                 and simds < self.Bt <= 2 * simds)

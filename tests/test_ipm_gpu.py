@@ -248,13 +248,21 @@ def _struct_problem(name, N, Bt):
     ("cartpole", 60, 96, "seq"),
     ("actuated_pendulum", 50, 64, "par"),  # registered, parametrised cost, nx = 3
     ("cartpole_track_limit", 60, 64, "par"),  # registered, traced cost with a state constraint
+    ("cartpole", 30, "split", "par"),      # #SIMDs + 77, default selection: the heavy-first split
 ])
 def test_structured_blocks_equal_dense_instance(name, N, Bt, mode, monkeypatch):
     """The persistent solver's structure-aware blocks (csrc/block_struct.h: only the variable
     entries of A, B, Q, R, M in the workspace, the constant ones rebuilt from literals and the
     family's parameters, products with structural zeros skipped) against the dense instance
-    (NOC_PERSIST_STRUCT=0): bit-identical controls and states, identical counters."""
-    monkeypatch.setenv("NOC_PERSIST_WIDE", "0")
+    (NOC_PERSIST_STRUCT=0): bit-identical controls and states, identical counters.  The split
+    case runs what the default selects at #SIMDs < B <= 2 #SIMDs: compact blocks with the
+    heavy-first split and its candidates, dense blocks without a split (both launches of a split
+    write the same block buffers, so they share one layout: ipm_persistent.hip heavy_count)."""
+    if Bt == "split":
+        monkeypatch.delenv("NOC_PERSIST_WIDE", raising=False)
+        Bt = 4 * torch.cuda.get_device_properties(0).multi_processor_count + 77
+    else:
+        monkeypatch.setenv("NOC_PERSIST_WIDE", "0")
     from noc import _lib
     from noc.ipm import BatchedIPM
     ocp, x0, u0 = _struct_problem(name, N, Bt)

@@ -168,6 +168,39 @@ def test_golden_fixtures_reproduced():
         assert _maxrel(L[k], gold[f"cart20/{k}"]) < 1e-12, k
 
 
+def test_golden_v3_schedule_solves_reproduced():
+    """golden_v3 (whole solves the GPU schedule tests are held to, tests/test_schedules_oracle_gpu.py):
+    the oracle regenerates two cart30 rows (par; seq for one) and one pend150 row -- counts exactly,
+    controls and final cost to 1e-12 -- and the rows are the seeded draws the fixture names."""
+    import sys
+    from oracle import noc_oracle as O, problems as PR
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "ip-parallel-optimal-control_amd"))
+    from noc import problems
+    gold = np.load(os.path.join(os.path.dirname(GOLDEN), "golden_v3.npz"))
+    draws = {"cart30": ("cartpole", 30, 24, 6), "cart200": ("cartpole", 200, 256, 11),
+             "pend150": ("pendulum", 150, 8, 3)}
+    for tag, (name, N, batch, seed) in draws.items():
+        x0, u0 = problems.initial_conditions(name, N, batch, seed=seed)
+        rows = gold[f"{tag}/rows"]
+        assert np.array_equal(gold[f"{tag}/x0"], x0[rows]) and np.array_equal(gold[f"{tag}/u0"], u0[rows])
+        exempt = rows == (int(gold["cart200/heavy_row"]) if tag == "cart200" else -1)
+        assert np.all(gold[f"{tag}/min_margin"][~exempt] >= 64) and exempt.sum() <= 1
+    assert list(gold["cart30/rows"]) == list(range(16))
+    for tag, tocp, k, seq in (("cart30", PR.cartpole_ocp(1.0 / 30), 2, False),
+                              ("cart30", PR.cartpole_ocp(1.0 / 30), 15, True),
+                              ("pend150", PR.pendulum_ocp(1.0 / 150), 3, False)):
+        prob = O.NumpyProblem(tocp)
+        g = lambda key: gold[f"{tag}/{key}"][k]
+        U, it, solves = O.par_interior_point_optimal_control(prob, g("u0"), g("x0"), terminal="stage0")
+        assert (it, solves) == (int(g("par_iters")), int(g("par_kkt_solves"))), (tag, k)
+        assert _maxrel(U, g("par_u")) < 1e-12, (tag, k)
+        cost = prob.total_cost(O.rollout(prob.dynamics, U, g("x0")), U, 0.0)
+        assert abs(cost - g("par_cost")) <= 1e-12 * abs(cost)
+        if seq:
+            Us, its = O.seq_interior_point_optimal_control(prob, g("u0"), g("x0"))
+            assert its == int(g("seq_iters")) and _maxrel(Us, g("seq_u")) < 1e-12
+
+
 def test_golden_v2_newton_blocks_reproduced():
     """golden_v2 (real c2 / c3 Newton blocks, faithful S:42-90 steps): the oracle regenerates the
     committed blocks and steps, and the faithful and symmetrised Riccati agree on them to 1e-12
