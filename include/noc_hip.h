@@ -295,6 +295,51 @@ int noc_debug_traj_times(long long* out, int n);
 int noc_ipm_solve(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, double bp0,
                   int max_solves, void* stream);
 
+/* ---- per-trajectory cost parameters ------------------------------------------------------------
+ * (Entry points added after NOC_ABI_VERSION 5; the version and the structs above are unchanged, so
+ * a caller detects them by symbol: dlsym / hasattr on noc_traj_params_supported.)
+ * A heterogeneous batch: trajectory b is solved with its own goal, wx, wu, wf and u_bound; dt,
+ * wrap_index, the linear family's A, B and the dynamics stay the family's.  `params` is one record
+ * of NOC_TRAJ_PARAM_DOUBLES doubles (256 bytes) per trajectory, (Bt, 32) row-major in device
+ * memory, 16-byte aligned, indexed by the trajectory (not by the workgroup: ws->order permutes
+ * workgroups only):
+ *   [ 0.. 7] goal[8]   [ 8..15] wx[8]   [16..19] wu[4]   [20..27] wf[8]   [28] u_bound
+ *   [29..31] reserved, zero
+ * Entries past the family's nx / nu are not read.  Every record must be complete (a field the
+ * caller does not vary repeats the family's value), finite, and its u_bound must be > 0 exactly
+ * when the family's is: a trajectory may move its bound, not switch the barrier on or off (the
+ * caller's contract, checked by the Python host; the library cannot read device memory without a
+ * sync).  The family's own goal, wx, wu, wf, u_bound are then not used.
+ * Results for trajectory b are bit for bit those of the shared-parameter entry point called on b
+ * alone with a noc_family that carries its record (same arithmetic on the same doubles).
+ * noc_traj_params_supported: 1 if the launch-per-phase entry points below cover (family, lanes) --
+ * the built-in families and a registered family with the parametrised cost, at the workspace lane
+ * counts of noc_ipm_step; 0 for a family with traced costs (it has no such parameters), an
+ * unknown family or other lanes.  The query is about (family, lanes) only: N must be >= 1 and is
+ * otherwise not looked at, and a 1 does not vouch for the workspace (its pointers, flags and dims
+ * are checked by each call).  noc_ipm_solve_params additionally needs noc_ipm_solve_supported.
+ * Contracts as the twins without _params (flags, resume, order, max_solves), except:
+ *   - dense blocks only (no _compact form);
+ *   - noc_ipm_solve_params always runs the one-wave kernel: never the wide kernel, speculative
+ *     candidates or the heavy-first split, whatever Bt and N;
+ *   - argument errors (NULL params, unsupported family, wrong lanes, an unknown flag bit) return
+ *     -1 with noc_last_error() set, before any device call. */
+#define NOC_TRAJ_PARAM_DOUBLES 32
+#define NOC_TP_GOAL 0
+#define NOC_TP_WX 8
+#define NOC_TP_WU 16
+#define NOC_TP_WF 20
+#define NOC_TP_UBOUND 28
+int noc_traj_params_supported(const noc_family* fam, int N, int lanes);
+int noc_ipm_solve_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                         int mode, int terminal, double bp0, int max_solves, void* stream);
+int noc_ipm_prepare_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                           int mode, int terminal, void* stream);
+int noc_ipm_trial_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                         int mode, void* stream);
+int noc_ipm_step_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                        int mode, int terminal, int lanes, void* stream);
+
 /* ---- building blocks of one Newton step: the reference's API functions as standalone batched
  * kernels (the fused solvers above inline them).  Natural layout, leading batch axis B. ---------
  * compute_derivatives (P:13-28 == S:10-25, D:10-25) of a family at (x (B,N+1,nx), u (B,N,nu)),

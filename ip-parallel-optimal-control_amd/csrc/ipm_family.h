@@ -234,6 +234,31 @@ struct Fam {
   }
 };
 
+// Per-trajectory cost parameters (include/noc_hip.h: NOC_TRAJ_PARAM_DOUBLES): the family q with
+// goal, wx, wu, wf, u_bound of trajectory b's record in place of its own.  The params kernels call
+// this once at entry on their own copy of the family argument and hand the copy to Fam /
+// BlockStruct / CompactSrc, so every consumer (BK_WX constants included) reads the trajectory's
+// values through the same expressions as the shared-parameter instances.  With a wave-uniform b
+// (the persistent solver, the trial kernel) the record is one aligned scalar burst and the fields
+// stay scalar operands.  In the linearise / costate / assemble kernels b is per thread (a block
+// spans several trajectories), so there every thread loads the fields its kernel reads as vector
+// loads (the unread ones are dropped by the compiler) on every launch: up to 29 doubles from a
+// 256-byte record shared by the trajectory's threads, next to the 36+ doubles of blocks per stage.
+// A params kernel guards this load by its own in-range test of b before the shared body runs; the
+// body's text is not touched (its twin must compile to what it did), so that test is restated
+// there: it alone keeps the record read in range, whatever the body's later exits are.
+template <int NX, int NU>
+NOC_DEV void load_traj_params(noc_family& q, const double* __restrict__ tp, int b) {
+  const double* __restrict__ r = tp + (size_t)b * NOC_TRAJ_PARAM_DOUBLES;
+  NOC_UNROLL for (int i = 0; i < NX; ++i) {
+    q.goal[i] = r[NOC_TP_GOAL + i];
+    q.wx[i] = r[NOC_TP_WX + i];
+    q.wf[i] = r[NOC_TP_WF + i];
+  }
+  NOC_UNROLL for (int j = 0; j < NU; ++j) q.wu[j] = r[NOC_TP_WU + j];
+  q.u_bound = r[NOC_TP_UBOUND];
+}
+
 // ------------------------------------------------------------------------------------------------
 NOC_DEV double readlane_d(double v, int lane) {  // wave-uniform broadcast of one lane's double
   const long long bits = __double_as_longlong(v);

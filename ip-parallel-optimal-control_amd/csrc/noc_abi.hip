@@ -686,4 +686,86 @@ static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, 
   return noc_ipm_trial(fam, ws, mode, stream);
 }
 
+// ---- per-trajectory cost parameters (include/noc_hip.h) ----------------------------------------
+int noc_traj_params_supported(const noc_family* fam, int N, int lanes) {
+  if (!fam || N < 1 || !noc::traj_params_supported(*fam)) return 0;
+  if (lanes == 1) return (fam->nx == 8 && fam->nu == 4) ? 1 : 0;  // grouped layout (check_ipm)
+  return (lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64) ? 1 : 0;
+}
+
+// the argument errors of the _params entry points, all -1, before any device call
+static int check_params(const char* who, const noc_family* fam, const noc_ipm_ws* ws,
+                        const double* params) {
+  const std::string w(who);
+  if (!fam || !ws) return fail(-1, w + ": family or workspace is NULL");
+  if (!params) return fail(-1, w + ": params is NULL (one record of 32 doubles per trajectory)");
+  if (reinterpret_cast<uintptr_t>(params) & 15) return fail(-1, w + ": params not 16-byte aligned");
+  if (!noc::traj_params_supported(*fam))
+    return fail(-1, w + ": unsupported family (unknown kind / nx / nu, or a registered family with "
+                        "traced costs, which has no goal / weights / bound)");
+  if (ws->flags & ~(NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP))
+    return fail(-1, w + ": workspace flags: unknown bits set");
+  if (!noc_traj_params_supported(fam, ws->N, ws->lanes))
+    return fail(-1, w + ": wrong lanes (" + std::to_string(ws->lanes) + ") or horizon for this family "
+                        "(noc_traj_params_supported)");
+  return check_ipm(fam, ws) ? -1 : 0;
+}
+
+int noc_ipm_prepare_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                           int mode, int terminal, void* stream) {
+  if (check_params("noc_ipm_prepare_params", fam, ws, params)) return -1;
+  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
+  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
+    return fail(-1, "bad terminal option");
+  if (ws->Bt == 0) return 0;
+  return hip_status(noc::ipm_prepare_params(*fam, *ws, params, mode, terminal,
+                                            static_cast<hipStream_t>(stream)), "ipm_prepare_params");
+}
+
+int noc_ipm_trial_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                         int mode, void* stream) {
+  if (check_params("noc_ipm_trial_params", fam, ws, params)) return -1;
+  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
+  if (ws->Bt == 0) return 0;
+  return hip_status(noc::ipm_trial_params(*fam, *ws, params, mode, static_cast<hipStream_t>(stream)),
+                    "ipm_trial_params");
+}
+
+int noc_ipm_step_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                        int mode, int terminal, int lanes, void* stream) {
+  if (ws && lanes != 0 && lanes != ws->lanes)
+    return fail(-1, "noc_ipm_step_params: lanes (" + std::to_string(lanes) + ") differs from the "
+                    "workspace's (" + std::to_string(ws->lanes) + "); pass 0 or ws->lanes");
+  int rc = noc_ipm_prepare_params(fam, ws, params, mode, terminal, stream);
+  if (rc) return rc;
+  // the dense KKT scan reads no cost parameter (the blocks carry them), then the params trial
+  const bool on_chip = noc_kkt_gains_on_chip(fam->nx, fam->nu, ws->N, ws->lanes) == 1;
+  rc = noc_kkt_solve_tiled(fam->nx, fam->nu, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q, ws->R,
+                           ws->M, ws->r, nullptr, nullptr, ws->P, nullptr, nullptr, ws->reg,
+                           ws->kkt_active, ws->dx, ws->du, ws->pred, ws->feasible,
+                           on_chip ? nullptr : ws->K, on_chip ? nullptr : ws->d, nullptr, nullptr,
+                           stream);
+  if (rc) return rc;
+  return noc_ipm_trial_params(fam, ws, params, mode, stream);
+}
+
+int noc_ipm_solve_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
+                         int mode, int terminal, double bp0, int max_solves, void* stream) {
+  if (fam && ws && params && noc::traj_params_supported(*fam) && ws->lanes != 64)
+    return fail(-1, "noc_ipm_solve_params: wrong lanes (" + std::to_string(ws->lanes) +
+                        "): the persistent solve needs workspace lanes = 64");
+  if (check_params("noc_ipm_solve_params", fam, ws, params)) return -1;
+  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
+  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
+    return fail(-1, "bad terminal option");
+  if (!(bp0 > 0.0)) return fail(-1, "bp0 must be > 0");
+  if (max_solves < 1) return fail(-1, "max_solves must be >= 1");
+  if (!noc::ipm_solve_supported(*fam, ws->N, ws->lanes))
+    return fail(-1, "noc_ipm_solve_params: unsupported family or horizon for the persistent solve "
+                    "(noc_ipm_solve_supported)");
+  if (ws->Bt == 0) return 0;
+  return hip_status(noc::ipm_solve_params(*fam, *ws, params, mode, terminal, bp0, max_solves,
+                                          static_cast<hipStream_t>(stream)), "ipm_solve_params");
+}
+
 }  // extern "C"

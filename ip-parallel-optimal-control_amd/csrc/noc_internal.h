@@ -254,6 +254,15 @@ int debug_phase_cycles(long long* out, int n, int reset);
 int debug_traj_times(long long* out, int n);
 hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal, double bp0,
                      int max_solves, hipStream_t s);
+// per-trajectory cost parameters (include/noc_hip.h: the _params entry points); tp: (Bt, 32)
+// records.  Dense blocks; the persistent form always runs the one-wave kernel.
+bool traj_params_supported(const noc_family& p);
+hipError_t ipm_prepare_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
+                              int terminal, hipStream_t s);
+hipError_t ipm_trial_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
+                            hipStream_t s);
+hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
+                            int terminal, double bp0, int max_solves, hipStream_t s);
 // wide whole-solve kernel (ipm_wide.hip): one 4-wave workgroup per trajectory, LDS-resident
 bool ipm_wide_supported(const noc_family& p, int N);
 size_t wide_lds_bytes(const noc_family& p, int N, int W);

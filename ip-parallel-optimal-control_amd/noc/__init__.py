@@ -6,3 +6,5 @@ KKT hot path runs in libnoc_hip.so (hand-written HIP for gfx950) through the C-A
 include/noc_hip.h.
 """
 __version__ = "0.1.0"
+
+from .traj_params import TrajectoryParams  # noqa: E402,F401  (pure numpy: loads no library)

@@ -113,6 +113,12 @@ SIGNATURES.update({
     "noc_debug_phase_cycles": (_i, [ctypes.POINTER(ctypes.c_longlong), _i, _i]),
     "noc_debug_traj_times": (_i, [ctypes.POINTER(ctypes.c_longlong), _i]),
     "noc_ipm_solve": (_i, [_fp, _wp, _i, _i, ctypes.c_double, _i, _dp]),
+    # per-trajectory cost parameters (added after ABI version 5: detected by symbol)
+    "noc_traj_params_supported": (_i, [_fp, _i, _i]),
+    "noc_ipm_solve_params": (_i, [_fp, _wp, _dp, _i, _i, ctypes.c_double, _i, _dp]),
+    "noc_ipm_prepare_params": (_i, [_fp, _wp, _dp, _i, _i, _dp]),
+    "noc_ipm_trial_params": (_i, [_fp, _wp, _dp, _i, _dp]),
+    "noc_ipm_step_params": (_i, [_fp, _wp, _dp, _i, _i, _i, _dp]),
     "noc_derivatives": (_i, [_fp, _i, _i] + [_dp] * 13 + [_dp]),
     "noc_final_cost_derivs": (_i, [_fp, _i, _dp, _dp, _dp, _dp]),
     "noc_costates": (_i, [_i, _i, _i, _dp, _dp, _dp, _dp, _i, _dp]),

@@ -69,7 +69,7 @@ def gather_rows(local: np.ndarray, batch: int, world: int) -> np.ndarray:
 def solve_sharded(ocp, controls, initial_state, mode=None, terminal=None,
                   engine_factory: Optional[Callable] = None, poll_every: int = 8,
                   bp0: float = 0.1, persistent: Optional[bool] = None,
-                  info: Optional[dict] = None):
+                  info: Optional[dict] = None, params=None):
     """Batched interior-point solve sharded over the process group.  Every rank passes the FULL
     batch (controls (B, N, nu), initial_state (B, nx)) and gets the full result back:
     (controls*, iterations, kkt_solves).
@@ -79,7 +79,9 @@ def solve_sharded(ocp, controls, initial_state, mode=None, terminal=None,
     all-reduce(MAX) of the convergence norm max|Hu| (P:158) -- SURVEY.md §8e's "RCCL only for the
     global convergence-norm all-reduce".  Otherwise the multi-launch loop polls the all-reduced
     "still running" count every `poll_every` iterations.  `info` (a dict) receives
-    convergence_norm and not_done (global)."""
+    convergence_norm and not_done (global).
+    params: per-trajectory cost parameters of the FULL batch (noc.TrajectoryParams); every rank
+    solves its shard with the rows shard_bounds gives it (dense blocks, BatchedIPM.load_params)."""
     from . import _lib
     mode = _lib.MODE_PAR if mode is None else mode
     if terminal is None:
@@ -96,8 +98,11 @@ def solve_sharded(ocp, controls, initial_state, mode=None, terminal=None,
             persistent = persistent_supported(ocp.family, N)
 
         def engine_factory(n, b):
-            return BatchedIPM(ocp.family, n, b, persistent=bool(persistent))
+            return BatchedIPM(ocp.family, n, b, persistent=bool(persistent),
+                              compact=False if params is not None else None)
     eng = engine_factory(N, max(hi - lo, 0))
+    if params is not None and hi > lo:
+        eng.load_params(params.rows(lo, hi))
     if persistent is None:
         persistent = bool(getattr(eng, "persistent", False))
     if persistent:

@@ -114,6 +114,7 @@ class BatchedIPM:
             setattr(ws, k, self.t[k].data_ptr())
         self.ws = ws
         self._lib = lib
+        self._params = None  # (Bt, 32) device records of load_params, or None: the family's own
         # overlapping rollouts on a second stream pays once a Newton step costs more than the
         # extra launch + event overhead (measured: c3 B*N = 819k faster, c2 B*N = 102k slower)
         self.overlap = (Bt * N >= 256 * 1024) if overlap is None else bool(overlap)
@@ -130,6 +131,27 @@ class BatchedIPM:
         self.t["u"].copy_(u)
         self.t["x0"].copy_(x0)
 
+    def load_params(self, params):
+        """Per-trajectory cost parameters (noc.traj_params.TrajectoryParams; None = back to the
+        family's shared ones).  With parameters loaded, solve / solve_persistent / step / prepare
+        call the noc_ipm_*_params entry points: dense blocks, one stream (no overlapped rollouts),
+        the one-wave persistent kernel without tail ladder or heavy-split probe; the "index",
+        "cost" and "probe" schedules work as before."""
+        if params is None:
+            self._params = None
+            return
+        from .traj_params import pack
+        rec = pack(params, self.family, self.Bt)  # ValueError on a bad field, before any device call
+        if self.compact:
+            raise _lib.NocError("per-trajectory parameters need dense blocks: build the engine with "
+                                "compact=False")
+        lib = self._lib
+        if not hasattr(lib, "noc_traj_params_supported") or lib.noc_traj_params_supported(
+                ctypes.byref(self.fam_c), self.N, self.lanes) != 1:
+            raise _lib.NocError("per-trajectory parameters: unsupported family or lanes "
+                                "(noc_traj_params_supported; a family with traced costs has none)")
+        self._params = torch.as_tensor(rec, device=self.device).contiguous()
+
     def _stream(self):
         return _lib.stream_handle(self.device)
 
@@ -140,6 +162,11 @@ class BatchedIPM:
             self.ev_main.record(torch.cuda.current_stream(self.device))
 
     def prepare(self, mode: int, terminal: int):
+        if self._params is not None:
+            _lib.check(self._lib.noc_ipm_prepare_params(
+                ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
+                terminal, self._stream()), "noc_ipm_prepare_params", self._lib)
+            return
         fn = self._lib.noc_ipm_prepare_compact if self.compact else self._lib.noc_ipm_prepare
         _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
                       self._stream()), "noc_ipm_prepare", self._lib)
@@ -147,6 +174,11 @@ class BatchedIPM:
     def step(self, mode: int, terminal: int):
         """One device iteration.  With overlap (default) the rollouts of trajectories that start
         a barrier stage run on a second stream beside the other trajectories' Newton step."""
+        if self._params is not None:  # per-trajectory parameters: one stream, dense blocks
+            _lib.check(self._lib.noc_ipm_step_params(
+                ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
+                terminal, self.lanes, self._stream()), "noc_ipm_step_params", self._lib)
+            return
         if not self.overlap:
             fn = self._lib.noc_ipm_step_compact if self.compact else self._lib.noc_ipm_step
             _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
@@ -184,7 +216,9 @@ class BatchedIPM:
         """Highest initial cost first: the initial total cost (P:142 at bp0, one rollout +
         linearisation, noc_ipm_prepare) is a cheap predictor of how many KKT solves a trajectory
         needs; a batch larger than the resident waves then starts its expected stragglers first
-        instead of in index order (longest-processing-time-first list scheduling)."""
+        instead of in index order (longest-processing-time-first list scheduling).  With
+        per-trajectory parameters loaded, prepare() runs the params kernels, so each trajectory is
+        ranked by the cost of its own problem (own goal, weights, bound), not the family's."""
         self.init(bp0)
         self.prepare(mode, terminal)
         return torch.argsort(self.t["cost"], descending=True, stable=True).to(torch.int32)
@@ -215,8 +249,13 @@ class BatchedIPM:
         if schedule not in ("auto", "cost", "index", "probe"):
             raise ValueError(schedule)
         auto = schedule == "auto"
-        tail = auto and not resume and self._tail_eligible()
-        if auto:
+        # per-trajectory parameters: the one-wave kernel only (noc_ipm_solve_params), so no tail
+        # ladder (its gathered resume runs speculative candidates) and no heavy-split probe
+        with_params = self._params is not None
+        tail = auto and not resume and not with_params and self._tail_eligible()
+        if auto and with_params:
+            schedule = "probe" if not resume and self.Bt > self._resident_slots() else "index"
+        elif auto:
             # the probe order also where the launcher splits off the costliest trajectories onto
             # speculative candidates (cart-pole, #SIMDs < B <= 2 #SIMDs: ipm_persistent.hip
             # heavy_count): 2048 cart-poles 20.4 -> 16.3-16.8 ms (profiles/r06/t/)
@@ -317,9 +356,15 @@ class BatchedIPM:
             self.ws.flags = flags | _lib.WS_RESUME
         self.ws.order = order.data_ptr() if order is not None else None
         try:
-            _lib.check(self._lib.noc_ipm_solve(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
-                                               mode, terminal, float(bp0), int(max_solves),
-                                               self._stream()), "noc_ipm_solve", self._lib)
+            if self._params is not None:
+                _lib.check(self._lib.noc_ipm_solve_params(
+                    ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
+                    terminal, float(bp0), int(max_solves), self._stream()),
+                    "noc_ipm_solve_params", self._lib)
+            else:
+                _lib.check(self._lib.noc_ipm_solve(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
+                                                   mode, terminal, float(bp0), int(max_solves),
+                                                   self._stream()), "noc_ipm_solve", self._lib)
         finally:
             self.ws.flags = flags
             self.ws.order = None

@@ -262,21 +262,29 @@ _ENGINE_CACHE_MAX = 8
 _ENGINE_CACHE_STAGES = 1 << 16  # Bt * N at most: B = 1 up to N = 65536, B = 64 at N = 1000
 
 
-def _engine(fam, N, Bt, lanes, device):
+def _engine(fam, N, Bt, lanes, device, dense=False):
+    """dense: a launch-per-phase engine with dense blocks (per-trajectory parameters need them);
+    a persistent engine manages its own blocks either way.  A reused engine comes back on the
+    shared-parameter path (load_params(None)): the caller loads this call's parameters, so a call
+    without any never solves with a previous call's."""
     from .ipm import persistent_supported
     # whole solve in one launch when the family / horizon allows it (same results, lanes 64)
     persistent = lanes in (0, 64) and persistent_supported(fam, N)
+    compact = False if (dense and not persistent) else None
     if Bt * N > _ENGINE_CACHE_STAGES:
-        return BatchedIPM(fam, N, Bt, device=device, lanes=lanes, persistent=persistent)
+        return BatchedIPM(fam, N, Bt, device=device, lanes=lanes, persistent=persistent,
+                          compact=compact)
     # per thread: an engine is a workspace, so two threads solving the same shape must not share
     # one (the reference's functions have no shared state)
     key = (id(fam), bytes(fam.to_c()), getattr(fam, "lib_path", None), N, Bt, lanes, persistent,
-           str(torch.device(device)), threading.get_ident())
+           str(torch.device(device)), threading.get_ident(), compact)
     with _ENGINES_LOCK:
         eng = _ENGINES.pop(key, None)
     if eng is None:
-        eng = BatchedIPM(fam, N, Bt, device=device, lanes=lanes, persistent=persistent)
+        eng = BatchedIPM(fam, N, Bt, device=device, lanes=lanes, persistent=persistent,
+                         compact=compact)
         eng._family_ref = fam  # keeps id(fam) from being reused while the entry lives
+    eng.load_params(None)
     with _ENGINES_LOCK:
         _ENGINES[key] = eng  # most recently used last
         while len(_ENGINES) > _ENGINE_CACHE_MAX:
@@ -285,7 +293,7 @@ def _engine(fam, N, Bt, lanes, device):
 
 
 def _run(ocp: OCP, controls, initial_state, mode, terminal="stage0", lanes=0,
-         device="cuda", return_info=False, one_stage_bp=None):
+         device="cuda", return_info=False, one_stage_bp=None, params=None):
     fam = _family(ocp)
     u = np.asarray(controls, dtype=np.float64)
     x0 = np.asarray(initial_state, dtype=np.float64)
@@ -293,7 +301,8 @@ def _run(ocp: OCP, controls, initial_state, mode, terminal="stage0", lanes=0,
     if single:
         u, x0 = u[None], x0[None]
     Bt, N, _ = u.shape
-    eng = _engine(fam, N, Bt, lanes, device)
+    eng = _engine(fam, N, Bt, lanes, device, dense=params is not None)
+    eng.load_params(params)  # None: the family's shared parameters
     eng.ws.flags = _lib.WS_ONE_STAGE if one_stage_bp is not None else 0
     eng.load(u, x0)
     bp0 = 0.1 if one_stage_bp is None else float(one_stage_bp)
@@ -308,13 +317,19 @@ def _run(ocp: OCP, controls, initial_state, mode, terminal="stage0", lanes=0,
     return U, iters
 
 
-def newton_oc(ocp: OCP, controls, initial_state, barrier_param, terminal="stage0"):
+def newton_oc(ocp: OCP, controls, initial_state, barrier_param, terminal="stage0", params=None):
     """P:127-225: ONE barrier stage -- rollout, then Newton iterations with the retry loop until
-    |Hu|inf < 1e-4 (or 1000 iterations) -> (states, controls, iterations)."""
-    return _run(ocp, controls, initial_state, _lib.MODE_PAR, terminal, one_stage_bp=barrier_param)
+    |Hu|inf < 1e-4 (or 1000 iterations) -> (states, controls, iterations).
+    params: per-trajectory cost parameters of a batched call (noc.TrajectoryParams)."""
+    return _run(ocp, controls, initial_state, _lib.MODE_PAR, terminal, one_stage_bp=barrier_param,
+                params=params)
 
 
 def par_interior_point_optimal_control(ocp: OCP, controls, initial_state, terminal="stage0",
-                                       lanes: int = 0, device="cuda", return_info=False):
-    """P:228-254: barrier 0.1 / 5^k while > 1e-4; Newton with retry loop; returns (u*, iters)."""
-    return _run(ocp, controls, initial_state, _lib.MODE_PAR, terminal, lanes, device, return_info)
+                                       lanes: int = 0, device="cuda", return_info=False,
+                                       params=None):
+    """P:228-254: barrier 0.1 / 5^k while > 1e-4; Newton with retry loop; returns (u*, iters).
+    params (noc.TrajectoryParams): a batched call solves trajectory b with its own goal, wx, wu,
+    wf, u_bound -- bit for bit the result of solving it alone with a family carrying them."""
+    return _run(ocp, controls, initial_state, _lib.MODE_PAR, terminal, lanes, device, return_info,
+                params=params)

@@ -67,13 +67,16 @@ def seq_solution(ocp: OCP, x, u, bp, rp):
     return dx, du, dV, feas, ru
 
 
-def newton_oc(ocp: OCP, controls, initial_state, bp):
-    """S:108-177: ONE barrier stage of the seq Newton loop -> (states, controls, iterations)."""
-    return _run(ocp, controls, initial_state, _lib.MODE_SEQ, "final_cost", one_stage_bp=bp)
+def newton_oc(ocp: OCP, controls, initial_state, bp, params=None):
+    """S:108-177: ONE barrier stage of the seq Newton loop -> (states, controls, iterations).
+    params: per-trajectory cost parameters of a batched call (noc.TrajectoryParams)."""
+    return _run(ocp, controls, initial_state, _lib.MODE_SEQ, "final_cost", one_stage_bp=bp,
+                params=params)
 
 
 def seq_interior_point_optimal_control(ocp: OCP, controls, initial_state, lanes: int = 0,
-                                       device="cuda", return_info=False):
-    """S:180-202: barrier 0.1 / 5^k while > 1e-4 -> (u*, iterations)."""
+                                       device="cuda", return_info=False, params=None):
+    """S:180-202: barrier 0.1 / 5^k while > 1e-4 -> (u*, iterations).
+    params: per-trajectory cost parameters of a batched call (noc.TrajectoryParams)."""
     return _run(ocp, controls, initial_state, _lib.MODE_SEQ, "final_cost", lanes, device,
-                return_info)
+                return_info, params=params)
