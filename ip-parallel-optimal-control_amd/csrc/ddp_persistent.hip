@@ -17,8 +17,10 @@
 //     stage-parallel with wave reductions (cost summed chunk-wise in stage order, then across
 //     lanes: the summation order of the multi-lane Newton kernels).
 // Every wave follows its own trajectory's reference control flow (outer Newton loop D:105-170,
-// retry loop D:114-152, barrier loop D:189-208).  Layout: natural, per trajectory contiguous
-// (x (Bt, N+1, nx), u (Bt, N, nu)); workspace include/noc_hip.h noc_ddp_work_doubles.
+// retry loop D:114-152, barrier loop D:189-208; the clip, the retry cap, the retry accounting and
+// the barrier step are the interior-point solvers': ipm_schedule.h).  Layout: natural, per
+// trajectory contiguous (x (Bt, N+1, nx), u (Bt, N, nu)); workspace include/noc_hip.h
+// noc_ddp_work_doubles.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -26,6 +28,7 @@
 
 #include "../../include/noc_hip.h"
 #include "ipm_family.h"
+#include "ipm_schedule.h"
 #include "noc_internal.h"
 
 namespace noc {
@@ -304,14 +307,13 @@ __global__ __launch_bounds__(64) void ddp_solve_kernel(noc_family prm, DdpArgs a
         rp = success ? rp * rp_shrink(gain)
                      : rp * reg_inc;                                // D:129-133: the OUTER reg_inc
         r_inc = success ? 2.0 : 2.0 * r_inc;                        // D:133
-        rp = fmin(fmax(rp, 1e-16), 1e16);                           // D:135
+        rp = rp_clip(rp);                                           // D:135
         inner += 1;
-        // identical retries at the rp clip (the par rule, noc_internal.h par_retry_repeats): a
+        // identical retries at the rp clip (the par rule, noc_internal.h retry_repeats): a
         // rejected pass at rp = 1e16 leaves every input of the next pass unchanged (records, X, U,
         // rp; reg_inc is the outer one), so the retries up to the cap repeat it bit for bit
-        if (a.skip_repeats && !g_ddp_trace && !success && rp == rp_used && inner <= 500) {
-          const int room = a.max_passes - passes;
-          const int k = (501 - inner) < room ? (501 - inner) : (room > 0 ? room : 0);
+        if (a.skip_repeats && !g_ddp_trace) {
+          const int k = retry_repeats(success, rp_used, rp, inner, a.max_passes - passes);
           inner += k;
           passes += k;
           r_inc = ldexp(r_inc, k);  // D:133 per retry
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(64) void ddp_solve_kernel(noc_family prm, DdpArgs a
           tr[5] = success ? 1.0 : 0.0; tr[6] = rp; tr[7] = hn; tr[8] = cost; tr[9] = new_cost;
         }
         if (passes >= a.max_passes) capped = true;
-        if (success || inner > 500 || capped) break;                // D:147-152
+        if (success || retry_cap_reached(inner) || capped) break;   // D:147-152
       }
       // the last trial becomes the nominal trajectory, accepted or not (D:154)
       double* t0 = X; X = TX; TX = t0;
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(64) void ddp_solve_kernel(noc_family prm, DdpArgs a
       if (capped) break;
     }
     total_it += it;  // D:196
-    bp = bp / 5.0;   // D:195
+    bp = next_barrier(bp);  // D:195
     if (a.one_stage) break;
   }
   // the final controls / states may live in the trial buffers: copy them out (lane-parallel)

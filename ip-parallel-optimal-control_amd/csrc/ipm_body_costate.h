@@ -140,6 +140,5 @@
   w.hu[b] = hu;                          // max |Hu| (P:158)
   const double gn = sqrt(g2s);           // ||cu||_F (P:116)
   w.gnorm[b] = gn;
-  // regularisation fed to the KKT solve: par R += rp*||cu||*I (P:116-118); seq Quu += mu*I (S:51)
-  w.reg[b] = (mode == NOC_MODE_PAR) ? w.rp[b] * gn : w.rp[b];
+  w.reg[b] = candidate_reg(mode, w.rp[b], gn);  // fed to the KKT solve (ipm_schedule.h)
   w.inner[b] = 0;

@@ -271,15 +271,6 @@ NOC_DEV double readlane_d(double v, int lane) {  // wave-uniform broadcast of on
 // test exactly as in the reference (P:158, P:199; D:120)
 NOC_DEV double nan_max(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 
-// The phase a persistent solve resumes at (NOC_WS_RESUME) from a workspace phase, including the
-// two-stream driver's intermediate ones: ROLLED (states current) continues with a new Newton
-// iteration, ROLLOUT_PENDING with the rollout.
-NOC_DEV int resume_phase(int ph) {
-  if (ph == NOC_PHASE_ROLLED) return NOC_PHASE_LINEARIZE;
-  if (ph == NOC_PHASE_ROLLOUT_PENDING) return NOC_PHASE_ROLLOUT;
-  return ph;
-}
-
 // wave-wide sum, every lane the same value: the __shfl_xor butterfly (off = 32 .. 1) with VALU
 // partners (small_linalg.h: segment_allreduce), bit-identical to the shuffle loop
 NOC_DEV double wave_sum(double v) {

@@ -9,8 +9,8 @@
 //                               (P:142), |Hu|inf (P:158), ||cu||_F (P:116), terminal Hessian
 //   assemble  (phase LINEARIZE) Q, R, M of compute_lqr_params (P:31-42)
 //   [kkt_scan (phase SOLVE)     par_Newton's solve, P:119-123]
-//   trial     (phase SOLVE)     trial point, feasibility, gain ratio, rp / r_inc update, accept,
-//                               Newton stop test, barrier schedule (P:156-254; seq mode S:121-202)
+//   trial     (phase SOLVE)     trial point, feasibility, then the accept rule and barrier
+//                               schedule of every solver (ipm_schedule.h; P:156-254, seq S:121-202)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "../../include/noc_hip.h"
 #include "block_struct.h"
 #include "ipm_family.h"
+#include "ipm_schedule.h"
 #include "noc_internal.h"
 #include "small_linalg.h"
 

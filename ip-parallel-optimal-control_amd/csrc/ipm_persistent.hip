@@ -9,8 +9,9 @@
 // no all-trajectory lockstep: a trajectory that needs 850 Newton steps no longer holds 4095 others
 // in per-step launches, and the per-step launch overhead is gone.
 //
-// Same arithmetic and state machine as the multi-launch driver (ipm_kernels.hip + the KKT scan
-// kernel at lanes = 64), so both produce identical iterates.  Lane l owns the horizon chunk of
+// The accept rule and barrier schedule are every solver's (ipm_schedule.h) and the arithmetic is
+// the multi-launch driver's (ipm_kernels.hip + the KKT scan kernel at lanes = 64), so both
+// produce identical iterates.  Lane l owns the horizon chunk of
 // the tiled layout (workspace lanes must be 64); cross-lane data moves through shuffles, the
 // KKT step stays in LDS (kkt_scan_wave with lds_out and dx = du = NULL), and the few hand-offs
 // through the workspace (rollout states, pred / feasible, the terminal Hessian) are ordered by a
@@ -21,6 +22,7 @@
 #include "../../include/noc_hip.h"
 #include "block_struct.h"
 #include "ipm_family.h"
+#include "ipm_schedule.h"
 #include "kkt_compact_src.h"
 #include "kkt_scan_impl.h"
 #include "noc_internal.h"
@@ -44,12 +46,8 @@ constexpr int PL = 64;  // lanes per trajectory in the persistent solver
 
 NOC_DEV void wave_fence() { __threadfence_block(); }
 
-// Wave-uniform solver state, parked in LDS across the KKT scan (whose register footprint is the
-// kernel's peak) instead of being kept live in VGPRs through it.
-struct IpmState {
-  double bp, rp, rinc, cost, hu, gnorm;
-  int it, inner, total_it, solves;
-};
+// The solver state (IpmState, ipm_schedule.h) is parked in LDS across the KKT scan (whose register
+// footprint is the kernel's peak) instead of being kept live in VGPRs through it.
 // Speculative candidates (SPEC > 1 waves per trajectory, one candidate regularisation each): the
 // scan's reg / pred / feasible of a wave's candidate, and its trial cost, exchanged through LDS.
 struct SpecIO {

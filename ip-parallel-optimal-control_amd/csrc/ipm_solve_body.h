@@ -56,15 +56,14 @@
     a.feasible = &io->feasible;
   }
 
-  double bp = bp0, rp = 1.0, rinc = 2.0, cost = 0.0, hu = 1.0, gnorm = 0.0;
-  int it = 0, inner = 0, total_it = 0, solves = 0;
+  IpmState sol;  // the solver state and its accept rule / barrier schedule: ipm_schedule.h
+  sol.init(bp0);
   bool capped = false;
   int phase = NOC_PHASE_DONE;     // the resume point a capped launch leaves in the workspace
   int entry = NOC_PHASE_ROLLOUT;  // RESUME: where this launch starts
   if constexpr (RESUME) {
-    bp = w.bp[b]; rp = w.rp[b]; rinc = w.rinc[b]; cost = w.cost[b]; hu = w.hu[b];
-    gnorm = w.gnorm[b]; it = w.it[b]; inner = w.inner[b]; total_it = w.total_it[b];
-    solves = w.kkt_solves[b]; entry = resume_phase(w.phase[b]);
+    sol.load(w, b);
+    entry = resume_phase(w.phase[b]);
     if (entry == NOC_PHASE_DONE) return;  // uniform over the wave
   } else {
     if (lead && w.repeats) w.repeats[b] = 0;
@@ -129,8 +128,8 @@
           f.jac(x, u, o.fx, o.fu);
           BS::template fold_consts<BF_A>(prm, o.fx);  // structural entries as literals / parameters
           BS::template fold_consts<BF_B>(prm, o.fu);
-          f.stage_grad(x, u, bp, o.cx, o.cu);
-          if (!lc_fresh) o.lc = f.stage_cost(x, u, bp);  // uniform over the wave
+          f.stage_grad(x, u, sol.bp, o.cx, o.cu);
+          if (!lc_fresh) o.lc = f.stage_cost(x, u, sol.bp);  // uniform over the wave
         };
         auto lin_store = [&](int j, const LinOut& o) {  // compact A, B: variable entries only
           double va[VA > 0 ? VA : 1], vb[VB > 0 ? VB : 1];
@@ -251,7 +250,7 @@
           load_xu(clampk(start + j), in.x, in.u);
           // cx, cu re-evaluated (the linearisation's values bit for bit) instead of stored and read
           // back: a workspace round trip of nx + nu doubles per stage against one stage_grad
-          f.stage_grad(in.x, in.u, bp, in.cx, in.cu);
+          f.stage_grad(in.x, in.u, sol.bp, in.cx, in.cu);
         };
         // LQ blocks at lambda_{k+1} (P:35-37): Q = cxx + l.fxx, R = cuu + l.fuu, M = cxu + l.fxu;
         // ru_k = cu_k + fu_k' lambda_{k+1} (P:34); then lambda_k = cx_k + fx_k' lambda_{k+1}
@@ -262,7 +261,7 @@
         };
         auto cost_compute = [&](const StageIn& in, bool valid, StageOut& o) {
           double Q[NX * NX], R[NU * NU];
-          f.stage_hess(in.x, in.u, bp, Q, R, o.M);
+          f.stage_hess(in.x, in.u, sol.bp, Q, R, o.M);
           f.add_hess_l(in.x, in.u, lam, Q, R, o.M);
           BS::template fold_consts<BF_M>(prm, o.M);
           NOC_UNROLL for (int i = 0; i < NX; ++i)
@@ -339,26 +338,23 @@
         }
         if (!keep_state) {
           // total_cost(x, u, bp) (P:142); x_N is the last lane's own (trial) store
-          cost = readlane_d(csum + f.final_cost(xN), PL - 1);
-          hu = hmax;                                      // max |Hu| (P:158)
-          gnorm = sqrt(g2s);                              // ||cu||_F (P:116)
-          inner = 0;
+          sol.cost = readlane_d(csum + f.final_cost(xN), PL - 1);
+          sol.hu = hmax;                                  // max |Hu| (P:158)
+          sol.gnorm = sqrt(g2s);                          // ||cu||_F (P:116)
+          sol.inner = 0;
         }
         keep_state = false;
-        // regularisation: par R += rp*||cu||*I (P:116-118); seq Quu += mu*I (S:51)
         relinearize = false;
       }
       // The candidates of this solve: candidate k is the regularisation the solver reaches after
-      // k rejected trials at this point (P:167-173 / S:139-144).  SPEC = 1: only k = 0, stored per
-      // trajectory as before; SPEC > 1: wave k solves candidate k (its LDS record).
+      // k rejected trials at this point (reg_update, ipm_schedule.h).  SPEC = 1: only k = 0, stored
+      // per trajectory as before; SPEC > 1: wave k solves candidate k (its LDS record).
       double c_reg[SPEC];
       {
-        double r = rp, ri = rinc;
+        double r = sol.rp, ri = sol.rinc;
         NOC_UNROLL for (int k = 0; k < SPEC; ++k) {
-          c_reg[k] = (mode == NOC_MODE_PAR) ? r * gnorm : r;
-          r = r * ri;
-          ri = 2.0 * ri;
-          if (mode == NOC_MODE_PAR) r = fmin(fmax(r, 1e-16), 1e16);
+          c_reg[k] = candidate_reg(mode, r, sol.gnorm);
+          reg_update(mode, false, 0.0, r, ri);
         }
       }
       if constexpr (SPEC == 1) {
@@ -375,11 +371,7 @@
       if constexpr (SPEC > 1) {
         if (relinearized) __syncthreads();
       }
-      {  // park the state (every lane stores the same values)
-        IpmState* st = state_slot<NX, NU>(N, SPEC, wv);
-        st->bp = bp; st->rp = rp; st->rinc = rinc; st->cost = cost; st->hu = hu; st->gnorm = gnorm;
-        st->it = it; st->inner = inner; st->total_it = total_it; st->solves = solves;
-      }
+      *state_slot<NX, NU>(N, SPEC, wv) = sol;  // park the state (every lane stores the same values)
       // ---------------- KKT solve (par_Newton, P:107-124) ----------------
       // HANDOFF on (phase 3 hands the chunk's first A, B to phase 4 in registers): the two-wave
       // cart-pole instance's scratch 524 -> 560 B/lane, but the solve is bound by its workspace
@@ -390,11 +382,7 @@
                           (SPEC > 1)>(a, b, l, src);
       }
       wave_fence();  // pred / feasible written by lane 0
-      {
-        const IpmState* st = state_slot<NX, NU>(N, SPEC, wv);
-        bp = st->bp; rp = st->rp; rinc = st->rinc; cost = st->cost; hu = st->hu; gnorm = st->gnorm;
-        it = st->it; inner = st->inner; total_it = st->total_it; solves = st->solves;
-      }
+      sol = *state_slot<NX, NU>(N, SPEC, wv);
       NOC_PHASE(3);
       // ---------------- trial point (P:156-175 / S:121-161) ----------------
       // (SPEC > 1: wave 0's trial costs go to w.lc -- the next linearisation's if its candidate is
@@ -412,8 +400,8 @@
           double xt0[NX], ut0[NU], xt1[NX], ut1[NU];
           trial_load(clampk(start + j), xt0, ut0);
           trial_load(clampk(start + j + 1), xt1, ut1);
-          const double c0 = f.stage_cost(xt0, ut0, bp);
-          const double c1 = f.stage_cost(xt1, ut1, bp);
+          const double c0 = f.stage_cost(xt0, ut0, sol.bp);
+          const double c1 = f.stage_cost(xt1, ut1, sol.bp);
           const bool f0 = f.feasible(xt0, ut0), f1 = f.feasible(xt1, ut1);
           if (j < len) { ok &= f0 ? 1 : 0; tsum += c0; if (lc_out) tstore<1, PL>(w.lc, b, j, l, cmax, &c0); }
           if (j + 1 < len) { ok &= f1 ? 1 : 0; tsum += c1; if (lc_out) tstore<1, PL>(w.lc, b, j + 1, l, cmax, &c1); }
@@ -423,7 +411,7 @@
           double xt[NX], ut[NU];
           trial_load(start + j, xt, ut);
           ok &= f.feasible(xt, ut) ? 1 : 0;
-          const double c = f.stage_cost(xt, ut, bp);
+          const double c = f.stage_cost(xt, ut, sol.bp);
           tsum += c;
           if (lc_out) tstore<1, PL>(w.lc, b, j, l, cmax, &c);  // the next linearisation's, if taken
         }
@@ -458,67 +446,20 @@
       // regularisation the one the sequential solver would use next (bit for bit) -- so the
       // decisions, counters and iterates are the sequential solver's.
       int winner = -1;
-      bool stop = false;
       NOC_UNROLL for (int k = 0; k < SPEC; ++k) {
-        if (k > 0) {
-          const double reg_next = (mode == NOC_MODE_PAR) ? rp * gnorm : rp;
-          if (stage_done || relinearize || reg_next != c_reg[k]) break;
-        }
-        const double new_cost = c_new[k];
-        const double pred = c_pred[k];
-        const bool bwd_ok = c_bwd[k];
-        const double gain = (new_cost - cost) / pred;             // P:164-165
-        const bool success = (gain > 0.0) && bwd_ok;              // P:166 / S:137
-#ifdef NOC_DECISION_TRACE
-        if (lead) NOC_TRACE_DECISION(g_dtrace, b, solves, bp, it, inner, cost, new_cost, pred, gain,
-                                     success, rp, rinc, hu, bwd_ok);
-#endif
-        const double shrink = rp_shrink(gain);  // P:169 / S:141 (noc_internal.h)
-        const double rp_used = rp;
-        rp = success ? rp * shrink : rp * rinc;                   // P:167-171 / S:139-143
-        rinc = success ? 2.0 : 2.0 * rinc;                        // P:172 / S:144
-        bool take, end_iter;
-        inner += 1;
-        if (mode == NOC_MODE_PAR) {
-          rp = fmin(fmax(rp, 1e-16), 1e16);                       // P:173
-          // identical retries at the rp clip: accounted, not recomputed (noc_internal.h)
-          const int rep = par_retry_repeats(w, success, rp_used, rp, inner, max_solves - solves - 1);
-          if (rep > 0) {
-            inner += rep;
-            solves += rep;
-            rinc = ldexp(rinc, rep);  // r_inc doubles per retry (P:172)
-            if (lead && w.repeats) w.repeats[b] += rep;
-          }
-          end_iter = success || inner > 500;                      // P:177-182
-          take = end_iter;                                        // last trial kept (P:175, P:184)
-          stop = end_iter && (hu < 1e-4 || it + 1 > 1000);        // P:199-202
-        } else {
-          take = success;                                         // S:145-146
-          end_iter = true;
-          stop = (hu < 1e-4) && bwd_ok;                           // S:157-161
-        }
-        if (take) winner = k;
+        if (k > 0 && (stage_done || relinearize || candidate_reg(mode, sol.rp, sol.gnorm) != c_reg[k])) break;
+        const AcceptOutcome o = accept_step(sol, mode, c_new[k], c_pred[k], c_bwd[k], w.flags,
+                                            max_solves - sol.solves - 1, lead ? &g_dtrace : nullptr, b);
+        if (o.rep > 0 && lead && w.repeats) w.repeats[b] += o.rep;
+        if (o.take) winner = k;
 #ifdef NOC_PERSIST_PROFILE
         if (b == 0 && lead) g_phase_cycles[5] += 1;
 #endif
-        solves += 1;
-        it += end_iter ? 1 : 0;
-        if (stop) {                                               // barrier stage finished
-          total_it += it;                                         // P:239 / S:187
-          bp = bp / 5.0;                                          // P:238 / S:186
-          it = 0;
-          rp = 1.0;                                               // P:134 / S:110
-          rinc = 2.0;                                             // P:135 / S:111
-          stage_done = true;
-        } else if (mode == NOC_MODE_PAR) {
-          relinearize = end_iter;
-        } else {
-          relinearize = success;  // a rejected seq step only changes the regularisation
-        }
-        if (solves >= max_solves) {  // capped: record where a later launch continues
+        stage_done = o.stage_done;
+        relinearize = o.relinearize;
+        if (sol.solves >= max_solves) {  // capped: record where a later launch continues
           capped = true;
-          phase = stage_done ? NOC_PHASE_ROLLOUT : (relinearize ? NOC_PHASE_LINEARIZE : NOC_PHASE_SOLVE);
-          if (stage_done && (!(bp > 1e-4) || (w.flags & NOC_WS_ONE_STAGE))) phase = NOC_PHASE_DONE;
+          phase = resume_point(stage_done, relinearize, sol.bp, w.flags);
           break;
         }
       }
@@ -536,7 +477,7 @@
       NOC_PHASE(4);
       if (capped) break;
     }
-    if (capped || !(bp > 1e-4)) break;                          // P:243-245
+    if (capped || !(sol.bp > 1e-4)) break;                      // P:243-245
     if (w.flags & NOC_WS_ONE_STAGE) break;                      // newton_oc: one stage
   }
   if constexpr (XLDS) {  // states and controls back to the workspace (every copy is the same)
@@ -547,18 +488,7 @@
     }
   }
   if (lead) {
-    w.bp[b] = bp;
-    w.rp[b] = rp;
-    w.rinc[b] = rinc;
-    w.cost[b] = cost;
-    w.hu[b] = hu;
-    w.gnorm[b] = gnorm;
-    w.it[b] = it;
-    w.inner[b] = inner;
-    w.total_it[b] = total_it;
-    w.kkt_solves[b] = solves;
-    w.kkt_active[b] = 0;
-    w.phase[b] = phase;
+    sol.store(w, b, phase);
 #ifdef NOC_PERSIST_PROFILE
     if (b < kTrajStamps) g_traj_times[b][1] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif

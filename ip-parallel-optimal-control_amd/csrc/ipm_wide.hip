@@ -2,8 +2,9 @@
 // W-wave workgroup (W = 4: 256 lanes), the trajectory's LQ blocks, states, controls and step held
 // in LDS for the whole solve (fp64, gfx950).
 //
-// Same reference control flow as ipm_persistent.hip (par_interior_point_optimal_control /
-// newton_oc, noc/par_interior_point_newton.py:127-254; seq S:108-202), for the regime where the
+// The reference control flow of par_interior_point_optimal_control / newton_oc (noc/
+// par_interior_point_newton.py:127-254; seq S:108-202) with the accept rule and barrier schedule of
+// every solver here (ipm_schedule.h), for the regime where the
 // batch does not fill the chip -- the reference's own B = 1 timing runs and the stragglers of a
 // large batch -- where a trajectory's latency is the wall time:
 //   * the stage-parallel work (linearise P:13-28, the costate sweep C:34-54 fused with the LQ
@@ -24,6 +25,7 @@
 #include "../../include/noc_hip.h"
 #include "block_struct.h"
 #include "ipm_family.h"
+#include "ipm_schedule.h"
 #include "kkt_scan_impl.h"
 #include "noc_internal.h"
 
@@ -199,13 +201,12 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
   for (int i = t; i < N * NU; i += T) su[(i % NU) * N + i / NU] = Ug[i];
   __syncthreads();
 
-  double bp = bp0, rp = 1.0, rinc = 2.0, cost = 0.0, hu = 1.0, gnorm = 0.0;
-  int it = 0, inner = 0, total_it = 0, solves = 0;
+  IpmState sol;  // the solver state and its accept rule / barrier schedule: ipm_schedule.h
+  sol.init(bp0);
   int phase = NOC_PHASE_ROLLOUT;  // where this launch starts (NOC_WS_RESUME) / stopped
   if (w.flags & NOC_WS_RESUME) {
-    bp = w.bp[b]; rp = w.rp[b]; rinc = w.rinc[b]; cost = w.cost[b]; hu = w.hu[b];
-    gnorm = w.gnorm[b]; it = w.it[b]; inner = w.inner[b]; total_it = w.total_it[b];
-    solves = w.kkt_solves[b]; phase = resume_phase(w.phase[b]);
+    sol.load(w, b);
+    phase = resume_phase(w.phase[b]);
   } else if (t == 0 && w.repeats) {
     w.repeats[b] = 0;
   }
@@ -247,12 +248,12 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
           f.jac(x, u, fx, fu);
           BS::template fold_consts<BF_A>(prm, fx);
           BS::template fold_consts<BF_B>(prm, fu);
-          f.stage_grad(x, u, bp, cx, cu);
+          f.stage_grad(x, u, sol.bp, cx, cu);
           bput<BS, BF_A>(sA, N, s, fx);
           bput<BS, BF_B>(sB, N, s, fu);
           fput<NX>(scx, N, s, cx);
           fput<NU>(scu, N, s, cu);
-          slc[s] = f.stage_cost(x, u, bp);
+          slc[s] = f.stage_cost(x, u, sol.bp);
         }
         NOC_WPHASE(1);
         // costates (C:34-54): chunk map lambda_start = G lambda_end + g, in-wave reverse scan,
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
           fget<NU>(scu, N, s, cu);
           // Q = cxx + l.fxx, R = cuu + l.fuu, M = cxu + l.fxu at l = lambda_{s+1} (P:35-37)
           double Qf[NX * NX], Rf[NU * NU], M[NX * NU], rr[NU];
-          f.stage_hess(x, u, bp, Qf, Rf, M);
+          f.stage_hess(x, u, sol.bp, Qf, Rf, M);
           f.add_hess_l(x, u, lam, Qf, Rf, M);
           BS::template fold_consts<BF_M>(prm, M);
           Sym<NX> Qs;
@@ -391,14 +392,14 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
         if (terminal == NOC_TERMINAL_FINAL_COST && last) f.final_hess(xN, sP);  // S:66
         const bool is_max[4] = {false, true, false, false};
         wg_reduce(red, 3, is_max);
-        cost = red[0] + f.final_cost(xN);  // total_cost(x, u, bp) (P:142)
-        hu = red[1];                       // max |Hu| (P:158)
-        gnorm = sqrt(red[2]);              // ||cu||_F (P:116)
-        if (!keep_inner) inner = 0;
+        sol.cost = red[0] + f.final_cost(xN);  // total_cost(x, u, bp) (P:142)
+        sol.hu = red[1];                       // max |Hu| (P:158)
+        sol.gnorm = sqrt(red[2]);              // ||cu||_F (P:116)
+        if (!keep_inner) sol.inner = 0;
         keep_inner = false;
         relinearize = false;
       }
-      const double reg = (mode == NOC_MODE_PAR) ? rp * gnorm : rp;  // P:116-118 / S:51
+      const double reg = candidate_reg(mode, sol.rp, sol.gnorm);
       __syncthreads();  // blocks and the terminal Hessian complete before the scan reads them
       NOC_WPHASE(2);
 #ifdef NOC_PERSIST_PROFILE
@@ -654,7 +655,7 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
         NOC_UNROLL for (int i = 0; i < NX; ++i) xt[i] = sx[(size_t)s * NX + i] + dxs(i, s);
         NOC_UNROLL for (int j = 0; j < NU; ++j) ut[j] = su[(size_t)j * N + s] + dus(j, s);
         ok &= f.feasible(xt, ut) ? 1 : 0;
-        tr[0] += f.stage_cost(xt, ut, bp);
+        tr[0] += f.stage_cost(xt, ut, sol.bp);
       }
       if (last) {
         double xt[NX];
@@ -667,37 +668,10 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
       }
       const bool traj_ok = __syncthreads_and(ok != 0);
       const double new_cost = traj_ok ? tr[0] : INFINITY;       // P:159-163, S:126-129
-      const double gain = (new_cost - cost) / pred;             // P:164-165
-      const bool success = (gain > 0.0) && bwd_ok;              // P:166 / S:137
-#ifdef NOC_DECISION_TRACE
-      if (t == 0) NOC_TRACE_DECISION(g_wide_dtrace, b, solves, bp, it, inner, cost, new_cost, pred,
-                                     gain, success, rp, rinc, hu, bwd_ok);
-#endif
-      const double shrink = rp_shrink(gain);  // P:169 / S:141 (noc_internal.h)
-      const double rp_used = rp;
-      rp = success ? rp * shrink : rp * rinc;                   // P:167-171 / S:139-143
-      rinc = success ? 2.0 : 2.0 * rinc;                        // P:172 / S:144
-      bool take, end_iter, stop;
-      inner += 1;
-      if (mode == NOC_MODE_PAR) {
-        rp = fmin(fmax(rp, 1e-16), 1e16);                       // P:173
-        // identical retries at the rp clip: accounted, not recomputed (noc_internal.h)
-        const int rep = par_retry_repeats(w, success, rp_used, rp, inner, max_solves - solves - 1);
-        if (rep > 0) {
-          inner += rep;
-          solves += rep;
-          rinc = ldexp(rinc, rep);  // r_inc doubles per retry (P:172)
-          if (t == 0 && w.repeats) w.repeats[b] += rep;
-        }
-        end_iter = success || inner > 500;                      // P:177-182
-        take = end_iter;                                        // last trial kept (P:175, P:184)
-        stop = end_iter && (hu < 1e-4 || it + 1 > 1000);        // P:199-202
-      } else {
-        take = success;                                         // S:145-146
-        end_iter = true;
-        stop = (hu < 1e-4) && bwd_ok;                           // S:157-161
-      }
-      if (take) {  // x <- x + dx, u <- u + du
+      const AcceptOutcome o = accept_step(sol, mode, new_cost, pred, bwd_ok, w.flags, max_solves - sol.solves - 1,
+                                          t == 0 ? &g_wide_dtrace : nullptr, b);
+      if (o.rep > 0 && t == 0 && w.repeats) w.repeats[b] += o.rep;
+      if (o.take) {  // x <- x + dx, u <- u + du
         for (int s = start; s < start + len; ++s) {
           NOC_UNROLL for (int i = 0; i < NX; ++i) sx[(size_t)s * NX + i] += dxs(i, s);
           NOC_UNROLL for (int j = 0; j < NU; ++j) su[(size_t)j * N + s] += dus(j, s);
@@ -709,44 +683,17 @@ __global__ __launch_bounds__(64 * W, 1) void ipm_wide_kernel(noc_family prm, noc
 #ifdef NOC_PERSIST_PROFILE
       if (b == 0 && t == 0) g_wide_cycles[5] += 1;
 #endif
-      solves += 1;
-      it += end_iter ? 1 : 0;
-      if (stop) {                                               // barrier stage finished
-        total_it += it;                                         // P:239 / S:187
-        bp = bp / 5.0;                                          // P:238 / S:186
-        it = 0;
-        rp = 1.0;                                               // P:134 / S:110
-        rinc = 2.0;                                             // P:135 / S:111
-        stage_done = true;
-      } else if (mode == NOC_MODE_PAR) {
-        relinearize = end_iter;
-      } else {
-        relinearize = success;  // a rejected seq step only changes the regularisation
-      }
-      // where a later launch would continue (the resume point)
-      phase = stage_done ? NOC_PHASE_ROLLOUT : (relinearize ? NOC_PHASE_LINEARIZE : NOC_PHASE_SOLVE);
-      if (stage_done && (!(bp > 1e-4) || (w.flags & NOC_WS_ONE_STAGE))) phase = NOC_PHASE_DONE;
-      if (phase == NOC_PHASE_DONE || solves >= max_solves) break;
+      stage_done = o.stage_done;
+      relinearize = o.relinearize;
+      phase = resume_point(stage_done, relinearize, sol.bp, w.flags);  // where a later launch would continue
+      if (phase == NOC_PHASE_DONE || sol.solves >= max_solves) break;
     }
-    if (phase != NOC_PHASE_ROLLOUT || solves >= max_solves) break;  // P:243-245 / capped
+    if (phase != NOC_PHASE_ROLLOUT || sol.solves >= max_solves) break;  // P:243-245 / capped
   }
   // results out: states, controls, the solver state
   for (int i = t; i < (N + 1) * NX; i += T) Xg[i] = sx[i];
   for (int i = t; i < N * NU; i += T) Ug[i] = su[(i % NU) * N + i / NU];
-  if (t == 0) {
-    w.bp[b] = bp;
-    w.rp[b] = rp;
-    w.rinc[b] = rinc;
-    w.cost[b] = cost;
-    w.hu[b] = hu;
-    w.gnorm[b] = gnorm;
-    w.it[b] = it;
-    w.inner[b] = inner;
-    w.total_it[b] = total_it;
-    w.kkt_solves[b] = solves;
-    w.kkt_active[b] = 0;
-    w.phase[b] = phase;
-  }
+  if (t == 0) sol.store(w, b, phase);
   __syncthreads();  // the next trajectory's controls overwrite the LDS read above
   }
 }

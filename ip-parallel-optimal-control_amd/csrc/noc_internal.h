@@ -139,18 +139,24 @@ __device__ __forceinline__ double rp_shrink(double gain) {
   const double c = 2.0 * gain - 1.0;
   return fmax(1.0 / 3.0, 1.0 - c * (c * c));
 }
+__device__ __forceinline__ double rp_clip(double rp) { return fmin(fmax(rp, 1e-16), 1e16); }  // P:173 / D:135
+__device__ __forceinline__ bool retry_cap_reached(int inner) { return inner > 500; }  // P:177-182 / D:147-152
 
-// Retry fixed point of the par inner loop (P:151-188).  A rejected trial whose rp was already at
-// the upper clip (P:173: rp * r_inc clipped back to 1e16) leaves every input of the next par_Newton
-// call unchanged -- x, u, the LQ blocks, rp -- so every remaining retry of the iteration repeats
+// Retry fixed point of the par inner loop (P:151-188; DDP: D:114-152).  A rejected trial whose rp
+// was already at the upper clip (rp * r_inc clipped back to 1e16) leaves every input of the next
+// solve unchanged -- x, u, the LQ blocks, rp -- so every remaining retry of the iteration repeats
 // this trial bit for bit (deterministic kernels) until the retry cap keeps it (P:175-184).  Returns
 // how many of those identical retries to account for without recomputing them (each one: a KKT
-// solve, inner += 1, r_inc *= 2), at most `room` (a max_solves cap); 0 when the shortcut is off.
-__device__ __forceinline__ int par_retry_repeats(const noc_ipm_ws& w, bool success, double rp_used,
-                                                 double rp_new, int inner, int room) {
-  if ((w.flags & NOC_WS_NO_REPEAT_SKIP) || success || rp_new != rp_used || inner > 500) return 0;
+// solve, inner += 1, r_inc *= 2), at most `room` (a max_solves cap).
+__device__ __forceinline__ int retry_repeats(bool success, double rp_used, double rp_new, int inner, int room) {
+  if (success || rp_new != rp_used || retry_cap_reached(inner)) return 0;
   const int k = 501 - inner;
   return room < k ? (room > 0 ? room : 0) : k;
+}
+// ... behind the workspace's switch (flags: noc_ipm_ws.flags); 0 when the shortcut is off
+__device__ __forceinline__ int par_retry_repeats(int flags, bool success, double rp_used, double rp_new,
+                                                 int inner, int room) {
+  return (flags & NOC_WS_NO_REPEAT_SKIP) ? 0 : retry_repeats(success, rp_used, rp_new, inner, room);
 }
 
 // Diagnostic decision trace of the persistent interior-point solvers (built only with
