@@ -431,6 +431,42 @@ int noc_nonlin_rollout(const noc_family* fam, int N, int B, const double* K, con
                        const double* x, const double* u, double* x_new, double* u_new,
                        void* stream);
 
+/* ---- per-trajectory cost parameters in interior-point DDP and the building blocks -------------
+ * (Entry points added after NOC_ABI_VERSION 5, like the noc_ipm_*_params ones above: detected by
+ * symbol, dlsym / hasattr on noc_ddp_params_supported.)  `params` is the (Bt, 32) record described
+ * there: trajectory b is solved / evaluated with its own goal, wx, wu, wf, u_bound, and its
+ * results are bit for bit those of the twin without _params called on b alone with a noc_family
+ * that carries its record.
+ * noc_ddp_params_supported: 1 iff noc_ddp_supported holds and the family has the parametrised
+ * cost (a registered family with traced costs has no such parameters).
+ * noc_ddp_solve_params: the contract of noc_ddp_solve_ex -- NOC_DDP_ONE_STAGE, the bp0 rule,
+ * max_passes, the NOC_DDP_NO_REPEAT_SKIP environment switch, noc_ddp_work_doubles of workspace;
+ * the record index is the trajectory index.
+ * noc_derivatives_params, noc_final_cost_derivs_params, noc_check_feasibility_params,
+ * noc_total_cost_params: their twins' arguments with `params` before the stream, for every family
+ * with the parametrised cost that the twin supports (nx = 8 included).  The other building blocks
+ * (noc_nonlin_rollout, noc_ddp_bwd_pass, noc_costates, noc_lqr_params) read no cost parameter and
+ * have no such form.
+ * Argument errors -- NULL params ("params is NULL"), params not 16-byte aligned, an unsupported
+ * family or one with traced costs ("unsupported family"), and whatever the twin refuses -- return
+ * -1 with noc_last_error() set, before any device call. */
+int noc_ddp_params_supported(const noc_family* fam);
+int noc_ddp_solve_params(const noc_family* fam, int N, int Bt, const double* x0, double* u,
+                         double* work, int* iterations, int* passes, int* done,
+                         const double* params, double bp0, int max_passes, int flags,
+                         void* stream);
+int noc_derivatives_params(const noc_family* fam, int N, int B, const double* x, const double* u,
+                           const double* bp, double* cx, double* cu, double* cxx, double* cuu,
+                           double* cxu, double* fx, double* fu, double* fxx, double* fuu,
+                           double* fxu, const double* params, void* stream);
+int noc_final_cost_derivs_params(const noc_family* fam, int B, const double* xN, double* grad,
+                                 double* hess, const double* params, void* stream);
+int noc_check_feasibility_params(const noc_family* fam, int N, int B, const double* x,
+                                 const double* u, int* feasible, const double* params,
+                                 void* stream);
+int noc_total_cost_params(const noc_family* fam, int N, int B, const double* x, const double* u,
+                          const double* bp, double* cost, const double* params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

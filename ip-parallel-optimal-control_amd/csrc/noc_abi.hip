@@ -768,4 +768,97 @@ int noc_ipm_solve_params(const noc_family* fam, const noc_ipm_ws* ws, const doub
                                           static_cast<hipStream_t>(stream)), "ipm_solve_params");
 }
 
+// ---- per-trajectory cost parameters in interior-point DDP and the building blocks -------------
+int noc_ddp_params_supported(const noc_family* fam) {
+  return (fam && noc::ddp_params_supported(*fam)) ? 1 : 0;
+}
+
+// the errors the _params forms add to their twins', all -1, before any device call
+static int check_block_params(const char* who, const noc_family* fam, const double* params, bool ddp) {
+  const std::string w(who);
+  if (!fam) return fail(-1, w + ": family is NULL");
+  if (!params) return fail(-1, w + ": params is NULL (one record of 32 doubles per trajectory)");
+  if (reinterpret_cast<uintptr_t>(params) & 15) return fail(-1, w + ": params not 16-byte aligned");
+  if (!noc::traj_params_supported(*fam))
+    return fail(-1, w + ": unsupported family (unknown kind / nx / nu, or a registered family with "
+                        "traced costs, which has no goal / weights / bound)");
+  if (ddp && !noc::ddp_params_supported(*fam))
+    return fail(-1, w + ": unsupported family for the one-launch DDP kernel: nx <= 4 "
+                        "(noc_ddp_params_supported)");
+  return 0;
+}
+
+int noc_ddp_solve_params(const noc_family* fam, int N, int Bt, const double* x0, double* u,
+                         double* work, int* iterations, int* passes, int* done,
+                         const double* params, double bp0, int max_passes, int flags, void* stream) {
+  if (check_block_params("noc_ddp_solve_params", fam, params, true)) return -1;
+  if (flags & ~NOC_DDP_ONE_STAGE) return fail(-1, "ddp flags: only NOC_DDP_ONE_STAGE is defined");
+  if (N < 1) return fail(-1, "horizon N must be >= 1");
+  if (Bt < 0) return fail(-1, "batch Bt must be >= 0");
+  if (!(bp0 >= 0.0) || !(bp0 < INFINITY)) return fail(-1, "bp0 must be finite and >= 0");  // noc_ddp_solve_ex
+  if (max_passes < 1) return fail(-1, "max_passes must be >= 1");
+  if (check_ptr(x0, "x0", true, 8) || check_ptr(u, "u", true, 8) || check_ptr(work, "work", true, 8) ||
+      check_ptr(iterations, "iterations", true, 4) || check_ptr(passes, "passes", true, 4) ||
+      check_ptr(done, "done", true, 4))
+    return -1;
+  if (Bt == 0) return 0;
+  return hip_status(noc::ddp_solve_params(*fam, N, Bt, x0, u, work, iterations, passes, done, params,
+                                          bp0, max_passes, flags, static_cast<hipStream_t>(stream)),
+                    "ddp_solve_params");
+}
+
+int noc_derivatives_params(const noc_family* fam, int N, int B, const double* x, const double* u,
+                           const double* bp, double* cx, double* cu, double* cxx, double* cuu,
+                           double* cxu, double* fx, double* fu, double* fxx, double* fuu,
+                           double* fxu, const double* params, void* stream) {
+  if (check_block_params("noc_derivatives_params", fam, params, false)) return -1;
+  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
+  const void* req[] = {x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
+  for (const void* p : req)
+    if (check_ptr(p, "derivatives argument", true, 8)) return -1;
+  if (B == 0) return 0;
+  noc::DerivArgs a{N, B, x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
+  return hip_status(noc::derivatives_params(*fam, a, params, static_cast<hipStream_t>(stream)),
+                    "derivatives_params");
+}
+
+int noc_final_cost_derivs_params(const noc_family* fam, int B, const double* xN, double* grad,
+                                 double* hess, const double* params, void* stream) {
+  if (check_block_params("noc_final_cost_derivs_params", fam, params, false)) return -1;
+  if (B < 0) return fail(-1, "need B >= 0");
+  if (check_ptr(xN, "xN", true, 8) || check_ptr(grad, "grad", true, 8) ||
+      check_ptr(hess, "hess", false, 8))
+    return -1;
+  if (B == 0) return 0;
+  return hip_status(noc::final_cost_derivs_params(*fam, B, xN, grad, hess, params,
+                                                  static_cast<hipStream_t>(stream)),
+                    "final_cost_derivs_params");
+}
+
+int noc_check_feasibility_params(const noc_family* fam, int N, int B, const double* x,
+                                 const double* u, int* feasible, const double* params,
+                                 void* stream) {
+  if (check_block_params("noc_check_feasibility_params", fam, params, false)) return -1;
+  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
+  if (check_ptr(x, "x", true, 8) || check_ptr(u, "u", true, 8) ||
+      check_ptr(feasible, "feasible", true, 4))
+    return -1;
+  if (B == 0) return 0;
+  return hip_status(noc::traj_feasibility_params(*fam, N, B, x, u, feasible, params,
+                                                 static_cast<hipStream_t>(stream)),
+                    "check_feasibility_params");
+}
+
+int noc_total_cost_params(const noc_family* fam, int N, int B, const double* x, const double* u,
+                          const double* bp, double* cost, const double* params, void* stream) {
+  if (check_block_params("noc_total_cost_params", fam, params, false)) return -1;
+  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
+  if (check_ptr(x, "x", true, 8) || check_ptr(u, "u", true, 8) || check_ptr(bp, "bp", true, 8) ||
+      check_ptr(cost, "cost", true, 8))
+    return -1;
+  if (B == 0) return 0;
+  return hip_status(noc::total_cost_params(*fam, N, B, x, u, bp, cost, params,
+                                           static_cast<hipStream_t>(stream)), "total_cost_params");
+}
+
 }  // extern "C"

@@ -269,6 +269,20 @@ hipError_t ipm_trial_params(const noc_family& p, const noc_ipm_ws& w, const doub
                             hipStream_t s);
 hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
                             int terminal, double bp0, int max_solves, hipStream_t s);
+// ... of interior-point DDP (ddp_persistent.hip: nx <= 4, the parametrised cost) and of the
+// building blocks that read a cost parameter (derivatives.hip: every family with that cost)
+bool ddp_params_supported(const noc_family& p);
+hipError_t ddp_solve_params(const noc_family& p, int N, int Bt, const double* x0, double* u,
+                            double* work, int* iterations, int* passes, int* done,
+                            const double* tp, double bp0, int max_passes, int flags,
+                            hipStream_t s);
+hipError_t derivatives_params(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s);
+hipError_t final_cost_derivs_params(const noc_family& p, int B, const double* xN, double* grad,
+                                    double* hess, const double* tp, hipStream_t s);
+hipError_t traj_feasibility_params(const noc_family& p, int N, int B, const double* x, const double* u,
+                                   int* ok, const double* tp, hipStream_t s);
+hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x, const double* u,
+                             const double* bp, double* cost, const double* tp, hipStream_t s);
 // wide whole-solve kernel (ipm_wide.hip): one 4-wave workgroup per trajectory, LDS-resident
 bool ipm_wide_supported(const noc_family& p, int N);
 size_t wide_lds_bytes(const noc_family& p, int N, int W);

@@ -131,6 +131,13 @@ SIGNATURES.update({
     "noc_ddp_solve_ex": (_i, [_fp, _i, _i] + [_dp] * 6 + [ctypes.c_double, _i, _i, _dp]),
     "noc_ddp_bwd_pass": (_i, [_i] * 4 + [_dp] * 18 + [_dp]),
     "noc_nonlin_rollout": (_i, [_fp, _i, _i] + [_dp] * 6 + [_dp]),
+    # per-trajectory cost parameters in DDP and the building blocks (detected by symbol)
+    "noc_ddp_params_supported": (_i, [_fp]),
+    "noc_ddp_solve_params": (_i, [_fp, _i, _i] + [_dp] * 6 + [_dp, ctypes.c_double, _i, _i, _dp]),
+    "noc_derivatives_params": (_i, [_fp, _i, _i] + [_dp] * 13 + [_dp, _dp]),
+    "noc_final_cost_derivs_params": (_i, [_fp, _i, _dp, _dp, _dp, _dp, _dp]),
+    "noc_check_feasibility_params": (_i, [_fp, _i, _i, _dp, _dp, _dp, _dp, _dp]),
+    "noc_total_cost_params": (_i, [_fp, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp]),
 })
 
 _lib: Optional[ctypes.CDLL] = None

@@ -27,9 +27,11 @@ def _dev(t, name="array"):
     return torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64), device="cuda")
 
 
-def final_cost_grad(ocp: OCP, final_state, hessian: bool = False):
+def final_cost_grad(ocp: OCP, final_state, hessian: bool = False, params=None):
     """grad(ocp.final_cost)(x_N) on the device (and hessian(final_cost) with hessian=True) for a
-    registered family: (B, nx) [, (B, nx, nx)] for batched x_N (B, nx), else unbatched."""
+    registered family: (B, nx) [, (B, nx, nx)] for batched x_N (B, nx), else unbatched.
+    params (noc.TrajectoryParams, batched x_N only): trajectory b's final cost takes its own goal
+    and wf (noc_final_cost_derivs_params)."""
     fam = getattr(ocp, "family", None)
     if fam is None:
         raise _lib.NocError("OCP has no registered device family (noc.problems / noc.families)")
@@ -40,6 +42,13 @@ def final_cost_grad(ocp: OCP, final_state, hessian: bool = False):
     g = torch.empty(B, fam.nx, dtype=torch.float64, device=xN.device)
     h = torch.empty(B, fam.nx, fam.nx, dtype=torch.float64, device=xN.device) if hessian else None
     lib = _lib.load_for(fam)
+    if params is not None:
+        from .traj_params import device_records
+        rec = device_records("final_cost_grad", params, fam, B, single, xN.device)
+        _lib.check(lib.noc_final_cost_derivs_params(
+            ctypes.byref(fam.to_c()), B, xN.data_ptr(), g.data_ptr(), _lib.ptr(h), rec.data_ptr(),
+            _lib.stream_handle(xN.device)), "noc_final_cost_derivs_params", lib)
+        return (g, h) if hessian else g
     _lib.check(lib.noc_final_cost_derivs(ctypes.byref(fam.to_c()), B, xN.data_ptr(), g.data_ptr(),
                                          _lib.ptr(h), _lib.stream_handle(xN.device)),
                "noc_final_cost_derivs", lib)

@@ -35,16 +35,20 @@ __all__ = ["compute_derivatives", "bwd_pass", "nonlin_rollout", "check_feasibili
            "interior_point_ddp"]
 
 
-def check_feasibility(ocp: OCP, x, u):
-    """D:93-95 (== P:45-47)."""
-    return check_traj_feasibility(ocp, x, u)
+def check_feasibility(ocp: OCP, x, u, params=None):
+    """D:93-95 (== P:45-47); params: as check_traj_feasibility."""
+    if params is None:
+        return check_traj_feasibility(ocp, x, u)
+    return check_traj_feasibility(ocp, x, u, params=params)
 
 
-def bwd_pass(final_cost, final_state, d: Derivatives, reg_param):
+def bwd_pass(final_cost, final_state, d: Derivatives, reg_param, params=None):
     """D:28-70: the DDP backward pass -> (ffgain k (N, nu), gain K (N, nu, nx), pred_reduction,
     feasible_bwd_pass, Hu (N, nu)).  Vx, Vxx at x_N are grad / hessian of `final_cost` (the OCP's
     callable, carrying its family, or the OCP itself); reg = reg_param * ||cu||_F.  Batched inputs
-    (leading B axis) give batched outputs."""
+    (leading B axis) give batched outputs.
+    params (noc.TrajectoryParams, batched inputs only): Vx, Vxx at x_N come from trajectory b's own
+    goal and wf; the recursion itself reads no cost parameter (d carries them)."""
     import torch
     from .costates import final_cost_grad
     fam = getattr(final_cost, "family", None)
@@ -74,7 +78,12 @@ def bwd_pass(final_cost, final_state, d: Derivatives, reg_param):
     if single:
         xN = xN[None]
         dd = Derivatives(*(t[None] for t in dd))
-    Vx, Vxx = final_cost_grad(_O, xN, hessian=True)
+    if params is None:
+        Vx, Vxx = final_cost_grad(_O, xN, hessian=True)
+    else:
+        if single:
+            raise _lib.NocError("bwd_pass: params needs batched inputs (a leading batch axis)")
+        Vx, Vxx = final_cost_grad(_O, xN, hessian=True, params=params)
     dev = dd.cu.device
     f64 = dict(dtype=torch.float64, device=dev)
     rp = torch.as_tensor(reg_param, **f64).reshape(-1).expand(B).contiguous()
@@ -92,25 +101,30 @@ def bwd_pass(final_cost, final_state, d: Derivatives, reg_param):
 
 
 def ddp(ocp: OCP, controls, initial_state, barrier_param, device="cuda",
-        max_passes: int = 10 ** 7):
+        max_passes: int = 10 ** 7, params=None):
     """D:98-186: ONE barrier value -- rollout, then DDP iterations with the retry loop until
-    |Hu|inf < 1e-4 (or 500 iterations) -> (states, controls, iterations)."""
+    |Hu|inf < 1e-4 (or 500 iterations) -> (states, controls, iterations).
+    params: per-trajectory cost parameters of a batched call (noc.TrajectoryParams)."""
     X, U, its, _ = _solve(ocp, controls, initial_state, device, float(barrier_param), max_passes,
-                          _lib.DDP_ONE_STAGE)
+                          _lib.DDP_ONE_STAGE, params)
     return X, U, its
 
 
 def interior_point_ddp(ocp: OCP, controls, initial_state, device="cuda", bp0: float = 0.1,
-                       max_passes: int = 10 ** 7, return_info: bool = False):
-    """D:189-208: barrier 0.1 / 5^k while > 1e-4, ddp (D:98-186) at each barrier value."""
-    X, Uh, itn, info = _solve(ocp, controls, initial_state, device, float(bp0), max_passes, 0)
+                       max_passes: int = 10 ** 7, return_info: bool = False, params=None):
+    """D:189-208: barrier 0.1 / 5^k while > 1e-4, ddp (D:98-186) at each barrier value.
+    params (noc.TrajectoryParams): a batched call solves trajectory b with its own goal, wx, wu,
+    wf, u_bound -- bit for bit the result of solving it alone with a family carrying them
+    (nx <= 4: noc_ddp_solve_params, one launch; larger states: the building-block loop)."""
+    X, Uh, itn, info = _solve(ocp, controls, initial_state, device, float(bp0), max_passes, 0,
+                              params)
     if return_info:
         info["states"] = X
         return Uh, itn, info
     return Uh, itn
 
 
-def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags):
+def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags, params=None):
     import torch
     if ocp.family is None:
         raise _lib.NocError("OCP has no registered device family (use noc.problems.*): the HIP "
@@ -130,6 +144,19 @@ def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags):
         u, x0 = u[None], x0[None]
     Bt, N, nu = u.shape
     nx = x0.shape[-1]
+    rec = None
+    if params is not None:  # every refusal on the host, before any device call
+        if single:
+            raise _lib.NocError("interior-point DDP: params needs batched inputs (controls "
+                                "(B, N, nu), initial_state (B, nx)): one record per trajectory")
+        # the parametrised cost (a registered family's traced costs have no goal / weights / bound)
+        if lib.noc_traj_params_supported(ctypes.byref(fam), 1, 64) != 1 or \
+                (not blocks and lib.noc_ddp_params_supported(ctypes.byref(fam)) != 1):
+            raise _lib.NocError("interior-point DDP: per-trajectory parameters need a family with "
+                                "the parametrised cost (noc_ddp_params_supported); a family with "
+                                "traced costs has none")
+        from .traj_params import pack
+        rec = pack(params, ocp.family, Bt)  # ValueError on a bad field
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.NocError("the MI355X path has no CPU fallback")
@@ -137,7 +164,9 @@ def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags):
     U = torch.as_tensor(np.ascontiguousarray(u), **f64)
     X0 = torch.as_tensor(np.ascontiguousarray(x0), **f64)
     if blocks:
-        Xd, Ud, itd, passd, doned = _solve_blocks(ocp, U, X0, bp0, max_passes, flags)
+        Xd, Ud, itd, passd, doned = _solve_blocks(
+            ocp, U, X0, bp0, max_passes, flags,
+            params=None if rec is None else torch.as_tensor(rec, **f64).contiguous())
         X, Uh, itn = Xd.cpu().numpy(), Ud.cpu().numpy(), itd.to(torch.int32).cpu().numpy()
         info = dict(passes=passd.to(torch.int32).cpu().numpy(), done=doned.cpu().numpy())
         if single:
@@ -147,11 +176,19 @@ def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags):
     work = torch.empty(int(lib.noc_ddp_work_doubles(nx, nu, N, Bt)), **f64)
     i32 = dict(device=dev, dtype=torch.int32)
     its, passes, done = (torch.zeros(Bt, **i32) for _ in range(3))
-    _lib.check(lib.noc_ddp_solve_ex(ctypes.byref(fam), N, Bt, _lib.ptr(X0), _lib.ptr(U),
-                                    _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
-                                    _lib.ptr(done), float(bp0), int(max_passes), int(flags),
-                                    _lib.stream_handle(dev)),
-               "noc_ddp_solve_ex", lib)
+    if rec is not None:
+        tp = torch.as_tensor(rec, **f64).contiguous()
+        _lib.check(lib.noc_ddp_solve_params(ctypes.byref(fam), N, Bt, _lib.ptr(X0), _lib.ptr(U),
+                                            _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
+                                            _lib.ptr(done), _lib.ptr(tp), float(bp0),
+                                            int(max_passes), int(flags), _lib.stream_handle(dev)),
+                   "noc_ddp_solve_params", lib)
+    else:
+        _lib.check(lib.noc_ddp_solve_ex(ctypes.byref(fam), N, Bt, _lib.ptr(X0), _lib.ptr(U),
+                                        _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
+                                        _lib.ptr(done), float(bp0), int(max_passes), int(flags),
+                                        _lib.stream_handle(dev)),
+                   "noc_ddp_solve_ex", lib)
     Uh, itn = U.cpu().numpy(), its.cpu().numpy()
     X = work[:Bt * (N + 1) * nx].view(Bt, N + 1, nx).cpu().numpy()
     info = dict(passes=passes.cpu().numpy(), done=done.cpu().numpy().astype(bool))
@@ -161,15 +198,20 @@ def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags):
     return X, Uh, itn, info
 
 
-def _solve_blocks(ocp, U, X0, bp0, max_passes, flags):
+def _solve_blocks(ocp, U, X0, bp0, max_passes, flags, params=None):
     """D:98-208 for the families the one-launch kernel does not instantiate (nx > 4: its lanes
     hold the value Hessian and the stage blocks in registers): the same control flow, every
     trajectory its own (masked updates), as a host loop over the device building blocks --
     noc_derivatives, noc_ddp_bwd_pass, noc_nonlin_rollout, noc_check_feasibility, noc_total_cost.
     One host synchronisation per retry (the loop conditions).  Returns final states, controls,
     iterations, backward passes (retries included) and done (not stopped by max_passes), all on
-    the device."""
+    the device.
+    params: the packed (Bt, 32) device record of per-trajectory cost parameters (or a
+    noc.TrajectoryParams), handed to the blocks that read a cost parameter -- total_cost,
+    compute_derivatives, check_traj_feasibility and bwd_pass (for Vx, Vxx at x_N); nonlin_rollout
+    reads none.  None: every block is called exactly as before."""
     import torch
+    pk = {} if params is None else dict(params=params)
     Bt, N, nu = U.shape
     nx = X0.shape[-1]
     dev = U.device
@@ -197,17 +239,17 @@ def _solve_blocks(ocp, U, X0, bp0, max_passes, flags):
         hu, it = torch.ones(Bt, **f64), torch.zeros(Bt, **i64)
         active = run.clone()
         while bool(active.any()):  # DDP iterations (D:105-170)
-            cost = total_cost(ocp, x, u, bp)  # D:108
-            d = compute_derivatives(ocp, x, u, bp)  # D:112
+            cost = total_cost(ocp, x, u, bp, **pk)  # D:108
+            d = compute_derivatives(ocp, x, u, bp, **pk)  # D:112
             rp, r_inc = reg_param.clone(), reg_inc.clone()
             inner = torch.zeros(Bt, **i64)
             tx, tu, hn = x.clone(), u.clone(), hu.clone()
             retry = active.clone()
             while bool(retry.any()):  # retry loop (D:114-152)
-                k, K, pred, feas, Hu = bwd_pass(ocp, x[:, -1], d, rp)
+                k, K, pred, feas, Hu = bwd_pass(ocp, x[:, -1], d, rp, **pk)
                 xt, ut = nonlin_rollout(ocp, K, k, x, u)
-                new_cost = torch.where(check_traj_feasibility(ocp, xt, ut),
-                                       total_cost(ocp, xt, ut, bp), inf)  # D:121-125
+                new_cost = torch.where(check_traj_feasibility(ocp, xt, ut, **pk),
+                                       total_cost(ocp, xt, ut, bp, **pk), inf)  # D:121-125
                 gain = (new_cost - cost) / pred
                 succ = (gain > 0) & feas
                 c = 2.0 * gain - 1.0  # x ** 3 as lax.integer_pow: c * (c * c), then 1 - it

@@ -136,13 +136,16 @@ def solve_sharded(ocp, controls, initial_state, mode=None, terminal=None,
 
 
 def ddp_sharded(ocp, controls, initial_state, ddp_fn: Optional[Callable] = None,
-                info: Optional[dict] = None, **kw):
+                info: Optional[dict] = None, params=None, **kw):
     """Batched interior-point DDP (noc.differential_dynamic_programming.interior_point_ddp, D:189-208)
     sharded over the process group like solve_sharded: every rank passes the FULL batch, solves its
     contiguous slice in one launch, and gets the full (controls*, iterations, passes) back.  No
     collective on the solve path; `info` receives the global backward-pass total and the number of
     trajectories a max_passes cap stopped early (two 8-byte all-reduces).  `ddp_fn(ocp, u, x0,
-    return_info=True, **kw) -> (U, its, info)` is injectable for CPU tests."""
+    return_info=True, **kw) -> (U, its, info)` is injectable for CPU tests.
+    params: per-trajectory cost parameters of the FULL batch (noc.TrajectoryParams); every rank's
+    `ddp_fn` gets `params=params.rows(lo, hi)`, the rows of its shard (no `params` keyword at all
+    when it is None)."""
     if ddp_fn is None:
         from .differential_dynamic_programming import interior_point_ddp as ddp_fn
     world, rank = dist.get_world_size(), dist.get_rank()
@@ -151,6 +154,8 @@ def ddp_sharded(ocp, controls, initial_state, ddp_fn: Optional[Callable] = None,
     B = u.shape[0]
     lo, hi = shard_bounds(B, world, rank)
     if hi > lo:
+        if params is not None:
+            kw = dict(kw, params=params.rows(lo, hi))
         U, its, inf = ddp_fn(ocp, u[lo:hi], x0[lo:hi], return_info=True, **kw)
         its = np.asarray(its, dtype=np.int32).reshape(-1)
         passes = np.asarray(inf["passes"], dtype=np.int32).reshape(-1)

@@ -28,6 +28,7 @@ import torch
 from . import _lib
 from .ipm import BatchedIPM
 from .optimal_control_problem import OCP, Derivatives
+from .traj_params import device_records
 
 _TERMINAL = {"final_cost": _lib.TERMINAL_FINAL_COST, "stage0": _lib.TERMINAL_STAGE0}
 
@@ -65,10 +66,12 @@ def _expect_shapes(fn: str, single: bool, B, items):
         raise _lib.NocError(f"{fn}: mis-shaped input: " + "; ".join(bad))
 
 
-def compute_derivatives(ocp: OCP, states, controls, bp) -> Derivatives:
+def compute_derivatives(ocp: OCP, states, controls, bp, params=None) -> Derivatives:
     """P:13-28: per-stage grad / hessian of stage_cost and jacrev / second derivatives of the
     dynamics at (x_k, u_k), k < N (noc_derivatives).  states (N+1, nx), controls (N, nu) (or
-    batched), bp a scalar or one per trajectory."""
+    batched), bp a scalar or one per trajectory.
+    params (noc.TrajectoryParams, batched inputs only): trajectory b's stage cost takes its own
+    goal, wx, wu, u_bound (noc_derivatives_params)."""
     fam = _family(ocp)
     nx, nu = fam.nx, fam.nu
     # every size from the states, the controls checked against them on the host, before anything
@@ -91,6 +94,13 @@ def compute_derivatives(ocp: OCP, states, controls, bp) -> Derivatives:
                   fu=(nx, nu), fxx=(nx, nx, nx), fuu=(nx, nu, nu), fxu=(nx, nx, nu))
     out = {k: torch.empty((B, N) + s, **f64) for k, s in shapes.items()}
     lib = _lib.load_for(fam)
+    if params is not None:
+        rec = device_records("compute_derivatives", params, fam, B, single, x.device)
+        _lib.check(lib.noc_derivatives_params(
+            ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(), bpt.data_ptr(),
+            *(out[k].data_ptr() for k in Derivatives._fields), rec.data_ptr(),
+            _lib.stream_handle(x.device)), "noc_derivatives_params", lib)
+        return Derivatives(*(out[k] for k in Derivatives._fields))
     _lib.check(lib.noc_derivatives(ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
                                    bpt.data_ptr(), *(out[k].data_ptr() for k in Derivatives._fields),
                                    _lib.stream_handle(x.device)), "noc_derivatives", lib)
@@ -130,12 +140,14 @@ def compute_lqr_params(lagrange_multipliers, d: Derivatives):
     return tuple(t[0] for t in res) if single else res
 
 
-def check_traj_feasibility(ocp: OCP, x, u):
+def check_traj_feasibility(ocp: OCP, x, u, params=None):
     """P:45-47: all(constraints(x_k, u_k) <= 0) over k < N (x[:-1] paired with u) with the
     family's whole constraint vector -- the built-ins' box on u, a registered family's traced
     constraints(x, u) including state constraints (noc_check_feasibility, one wave per
     trajectory).  x (N+1, nx), u (N, nu) -> a 0-d bool tensor; batched (B, N+1, nx), (B, N, nu)
-    -> (B,) bool."""
+    -> (B,) bool.
+    params (noc.TrajectoryParams, batched inputs only): trajectory b is tested against its own
+    u_bound (noc_check_feasibility_params)."""
     fam = _family(ocp)
     x, u = _dev(x, "x"), _dev(u, "u")
     single = u.dim() == 2
@@ -146,11 +158,19 @@ def check_traj_feasibility(ocp: OCP, x, u):
         raise _lib.NocError(f"check_traj_feasibility: need x (B, N+1, {fam.nx}) and u (B, N, "
                             f"{fam.nu}); got {tuple(x.shape)} and {tuple(u.shape)}")
     B, N = u.shape[0], u.shape[1]
+    rec = None if params is None else device_records("check_traj_feasibility", params, fam, B,
+                                                     single, u.device)
     if N == 0:  # jnp.all of an empty constraint array
         ok = torch.ones(B, dtype=torch.bool, device=u.device)
         return ok[0] if single else ok
     ok = torch.empty(B, dtype=torch.int32, device=u.device)
     lib = _lib.load_for(fam)
+    if rec is not None:
+        _lib.check(lib.noc_check_feasibility_params(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
+                                                    u.data_ptr(), ok.data_ptr(), rec.data_ptr(),
+                                                    _lib.stream_handle(u.device)),
+                   "noc_check_feasibility_params", lib)
+        return ok.bool()
     _lib.check(lib.noc_check_feasibility(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
                                          u.data_ptr(), ok.data_ptr(),
                                          _lib.stream_handle(u.device)),
@@ -159,11 +179,13 @@ def check_traj_feasibility(ocp: OCP, x, u):
     return ok[0] if single else ok
 
 
-def total_cost(ocp: OCP, states, controls, bp):
+def total_cost(ocp: OCP, states, controls, bp, params=None):
     """ocp.total_cost(states, controls, bp) on the device (PR:53-56, CR:48-51, LD:45-48; a
     registered family's own traced costs): final_cost(x_N) + sum_k stage_cost(x_k, u_k, bp)
     (noc_total_cost, one wave per trajectory).  states (N+1, nx), controls (N, nu) -> a 0-d
-    tensor; batched -> (B,); bp a scalar or one per trajectory."""
+    tensor; batched -> (B,); bp a scalar or one per trajectory.
+    params (noc.TrajectoryParams, batched inputs only): trajectory b's cost takes its own goal,
+    wx, wu, wf, u_bound (noc_total_cost_params)."""
     fam = _family(ocp)
     us = _shape(controls)
     single = len(us) == 2
@@ -180,6 +202,13 @@ def total_cost(ocp: OCP, states, controls, bp):
     bpt = torch.as_tensor(bp, dtype=torch.float64, device=u.device).reshape(-1).expand(B).contiguous()
     cost = torch.empty(B, dtype=torch.float64, device=u.device)
     lib = _lib.load_for(fam)
+    if params is not None:
+        rec = device_records("total_cost", params, fam, B, single, u.device)
+        _lib.check(lib.noc_total_cost_params(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
+                                             u.data_ptr(), bpt.data_ptr(), cost.data_ptr(),
+                                             rec.data_ptr(), _lib.stream_handle(u.device)),
+                   "noc_total_cost_params", lib)
+        return cost
     _lib.check(lib.noc_total_cost(ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
                                   bpt.data_ptr(), cost.data_ptr(), _lib.stream_handle(u.device)),
                "noc_total_cost", lib)

@@ -51,9 +51,11 @@ def fwd_pass(gain, ff_gain, d: Derivatives):
     return lqt.fwd_pass(_dev(d.fx), _dev(d.fu), _dev(gain), _dev(ff_gain))
 
 
-def check_feasibility(ocp: OCP, x, u):
-    """S:93-95."""
-    return check_traj_feasibility(ocp, x, u)
+def check_feasibility(ocp: OCP, x, u, params=None):
+    """S:93-95; params: as check_traj_feasibility."""
+    if params is None:
+        return check_traj_feasibility(ocp, x, u)
+    return check_traj_feasibility(ocp, x, u, params=params)
 
 
 def seq_solution(ocp: OCP, x, u, bp, rp):

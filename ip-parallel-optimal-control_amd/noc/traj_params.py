@@ -3,7 +3,8 @@
 A heterogeneous batch solves trajectory b with its own goal, wx, wu, wf and u_bound; dt,
 wrap_index, the linear family's A, B and the dynamics stay the family's.  TrajectoryParams names
 the fields a caller varies; pack() turns it, against a Family, into the (Bt, 32) record the
-noc_ipm_*_params entry points read.  Pure numpy: no device and no library are needed to pack.
+noc_*_params entry points read.  Pure numpy: no device and no library are needed to pack
+(device_records puts a packed record on the device for the building blocks).
 """
 from __future__ import annotations
 
@@ -80,3 +81,23 @@ def pack(params: TrajectoryParams, family, Bt: int) -> np.ndarray:
             raise ValueError("TrajectoryParams.u_bound must be > 0 for a family with a control bound")
         rec[:, _UBOUND] = ub
     return rec
+
+
+def device_records(fn: str, params, family, B: int, single: bool, device):
+    """The (B, 32) fp64 device tensor a noc_*_params building block reads: `params` packed against
+    `family` (ValueError on a bad field), or `params` itself when it already is such a tensor (a
+    loop over the blocks packs once: differential_dynamic_programming._solve_blocks).  NocError for
+    an unbatched call (the record is per trajectory of a batch) or a mis-shaped record, before
+    anything reaches the device."""
+    import torch
+    from . import _lib
+    if single:
+        raise _lib.NocError(f"{fn}: params needs batched inputs (a leading batch axis): one "
+                            f"record per trajectory")
+    if isinstance(params, torch.Tensor):
+        if tuple(params.shape) != (B, PARAM_DOUBLES) or params.dtype != torch.float64:
+            raise _lib.NocError(f"{fn}: a packed params record must be a ({B}, {PARAM_DOUBLES}) "
+                                f"float64 tensor; got {tuple(params.shape)} {params.dtype}")
+        _lib.require_device(params, "params")
+        return params.contiguous()
+    return torch.as_tensor(pack(params, family, B), device=device).contiguous()
