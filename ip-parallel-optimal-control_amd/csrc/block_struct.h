@@ -262,6 +262,16 @@ struct BlockStruct {
   // may A(k, j) / B(k, j) be nonzero (the scan's arithmetic skips the products with the others)
   static constexpr bool nzA(int k, int j) { return ((kNzA >> (k * NX + j)) & 1) != 0; }
   static constexpr bool nzB(int k, int j) { return ((kNzB >> (k * NU + j)) & 1) != 0; }
+  // The closed-loop map F = A + B K, f = B k: where row k of B is structurally zero, row k of F is
+  // row k of A (its zeros are exact zeros again) and f[k] is exactly 0 (non-affine scan; with an
+  // affine term f[k] = c[k], so the scan asks nzf only where it has none)
+  static constexpr bool nzBrow(int k) {
+    for (int u = 0; u < NU; ++u)
+      if (nzB(k, u)) return true;
+    return false;
+  }
+  static constexpr bool nzF(int k, int j) { return nzBrow(k) || nzA(k, j); }
+  static constexpr bool nzf(int k) { return nzBrow(k); }
 
   template <int K>
   NOC_DEV static double value(const noc_family& p, double lit, int idx, double delta) {

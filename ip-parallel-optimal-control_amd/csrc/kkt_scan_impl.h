@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "small_linalg.h"
 #include "noc_internal.h"
 
@@ -75,11 +77,15 @@ static __device__ long long g_scan_sub[8];
 
 // Which entries of a stage's A, B may be nonzero: the generic scan takes every one; the persistent
 // solver's structure-aware blocks (block_struct.h: BlockStruct) skip the products with structural
-// zeros.  nzA / nzB are called with unrolled (compile-time) indices.
+// zeros.  nzA / nzB are called with unrolled (compile-time) indices.  nzF / nzf: the same for the
+// closed-loop map F = A + B K and (non-affine) f = B k, whose rows with a structurally zero row of
+// B are A's rows and exact zeros.
 template <int NX, int NU>
 struct DenseBlocks {
   static constexpr bool nzA(int, int) { return true; }
   static constexpr bool nzB(int, int) { return true; }
+  static constexpr bool nzF(int, int) { return true; }
+  static constexpr bool nzf(int) { return true; }
 };
 
 template <int NX, int NU>
@@ -290,14 +296,15 @@ NOC_DEV void prepend(Elem<NX>& e, const StageData<NX, NU>& st, double reg) {
     NOC_UNROLL for (int t = 0; t < NU; ++t) if (ST::nzB(i, t)) s -= st.B(i, t) * Y[t][NX];
     f[i] = s;
   }
+  // (the products with F's and f's structural zeros skipped, as nzA / nzB above: nzF / nzf)
   Mat<NX, NX> An;
   NOC_UNROLL for (int i = 0; i < NX; ++i) {
     double sb = e.b[i];
-    NOC_UNROLL for (int k = 0; k < NX; ++k) sb += e.A(i, k) * f[k];
+    NOC_UNROLL for (int k = 0; k < NX; ++k) if (AFF || ST::nzf(k)) sb += e.A(i, k) * f[k];
     e.b[i] = sb;
     NOC_UNROLL for (int j = 0; j < NX; ++j) {
       double s = 0.0;
-      NOC_UNROLL for (int k = 0; k < NX; ++k) s += e.A(i, k) * F(k, j);
+      NOC_UNROLL for (int k = 0; k < NX; ++k) if (ST::nzF(k, j)) s += e.A(i, k) * F(k, j);
       An(i, j) = s;
     }
   }
@@ -618,8 +625,14 @@ struct ArgsSrc {
 // IO0: reg, pred and feasible are one slot each (a.reg[0], a.pred[0], a.feasible[0]) instead of
 // per-trajectory arrays -- the persistent solver's speculative candidates (ipm_persistent.hip: SPEC)
 // each solve the same blocks with their own regularisation and keep those three in LDS.
+// PEEL (the stand-alone scan kernels): the first stage a lane runs in phase 3, where Phi = I and
+// phi = 0 still, assigns Phi = F, phi = f instead of forming I * F and 0 + I * f (riccati_stage).
+// Off inside the persistent solvers: the extra copy of the stage costs their instances registers
+// (pendulum 158 -> 168-170 VGPRs and 3 -> 2 waves per SIMD, cart-pole two-wave 352 -> 376-448 B of
+// scratch, compiler's resource report) for 8-56 FMAs per chunk.
 template <int NX, int NU, int L, bool AFF, bool TILED, class SRC, int CACHE = 0, bool HANDOFF = true,
-          bool BIG = false, bool NT3 = false, bool AB = (BIG && ab_supported<NX, NU>()), bool IO0 = false>
+          bool BIG = false, bool NT3 = false, bool AB = (BIG && ab_supported<NX, NU>()), bool IO0 = false,
+          bool PEEL = false>
 NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, const SRC& src) {
   constexpr int KD = kd_width<NX, NU>();
   using ST = typename SRC::Struct;  // structural zeros of A, B (DenseBlocks: none)
@@ -767,7 +780,9 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
       if constexpr (NT3) src_re.stage_last(s, s - start, reg, st);
       else src_re.stage(s, s - start, reg, st);
     };
-    auto riccati_stage = [&](const int s, const StageData<NX, NU>& st) {
+    // first: the lane's first executed stage (s = start + len - 1), where Phi = I, phi = 0 still --
+    // std::true_type / std::false_type where the call site knows it, a bool where it does not
+    auto riccati_stage = [&](const int s, const StageData<NX, NU>& st, const auto first) {
       Mat<NX, NX> SA;
       Mat<NX, NU> SB;
       NOC_UNROLL for (int i = 0; i < NX; ++i) {
@@ -860,22 +875,36 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         NOC_UNROLL for (int u = 0; u < NU; ++u) if (ST::nzB(i, u)) t += st.B(i, u) * Kk[NU * NX + u];
         f[i] = t;
       }
-      Mat<NX, NX> Pn;
-      NOC_UNROLL for (int i = 0; i < NX; ++i) {
-        double t = phi[i];
-        NOC_UNROLL for (int k = 0; k < NX; ++k) t += Phi(i, k) * f[k];
-        phi[i] = t;
-        NOC_UNROLL for (int j = 0; j < NX; ++j) {
-          double u = 0.0;
-          NOC_UNROLL for (int k = 0; k < NX; ++k) u += Phi(i, k) * F(k, j);
-          Pn(i, j) = u;
+      if (PEEL && first) {
+        // Phi = I, phi = 0: the products below would be I * F and 0 + I * f, sums that start at
+        // 0.0 and add exact zeros around the one term 1 * x -- the same doubles as F and f for
+        // finite entries, except that an entry of F or f that is -0.0 comes out of the sums as
+        // +0.0 and is kept as -0.0 here (equal under ==; every later use is a product or a sum,
+        // so at most the sign of a zero differs downstream)
+        Phi = F;
+        phi = f;
+      } else {
+        // (the products with F's and f's structural zeros skipped: nzF / nzf)
+        Mat<NX, NX> Pn;
+        NOC_UNROLL for (int i = 0; i < NX; ++i) {
+          double t = phi[i];
+          NOC_UNROLL for (int k = 0; k < NX; ++k) if (AFF || ST::nzf(k)) t += Phi(i, k) * f[k];
+          phi[i] = t;
+          NOC_UNROLL for (int j = 0; j < NX; ++j) {
+            double u = 0.0;
+            NOC_UNROLL for (int k = 0; k < NX; ++k) if (ST::nzF(k, j)) u += Phi(i, k) * F(k, j);
+            Pn(i, j) = u;
+          }
         }
+        Phi = Pn;
       }
-      Phi = Pn;
     };
+    const int sfirst = start + len - 1;  // the lane's first executed stage
+    constexpr std::true_type kFirst{};
+    constexpr std::false_type kLater{};
     if constexpr (CACHE > 0) {
       NOC_UNROLL for (int jj = CACHE - 1; jj >= 0; --jj)
-        if (jj < len) riccati_stage(start + jj, cache[jj]);
+        if (jj < len) riccati_stage(start + jj, cache[jj], jj == len - 1);
     } else {
       // not software pipelined: prefetching stage s-1 during stage s (registers) was measured
       // slower (phase 3 44k -> 60k cycles per wave at c3: the prefetch spills, and the phase runs
@@ -890,25 +919,34 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
           for (int s = start + len - 1; s >= start + jl; --s) {
             StageData<NX, NU> st;
             stage3(s, st);
-            riccati_stage(s, st);
+            riccati_stage(s, st, s == sfirst);
           }
           for (int s = start + jl - 1; s >= start; --s) {
             StageData<NX, NU> st;
             src_re.template stage_part<3, NT3>(s, s - start, reg, st);
             ab_load<NX, NU>(lab, s - start, st.A, st.B);
-            riccati_stage(s, st);
+            riccati_stage(s, st, s == sfirst);
           }
         }
       } else if constexpr (HANDOFF) {
-        for (int s = start + len - 1; s > start; --s) {
+        // the first executed stage peeled too (Phi = F, phi = f: riccati_stage): every lane with
+        // more than one stage takes it in the same iteration, so the wave does not diverge
+        int s = sfirst;
+        if (PEEL && len > 1) {
           StageData<NX, NU> st;
           stage3(s, st);
-          riccati_stage(s, st);
+          riccati_stage(s, st, kFirst);
+          --s;
+        }
+        for (; s > start; --s) {
+          StageData<NX, NU> st;
+          stage3(s, st);
+          riccati_stage(s, st, kLater);
         }
         if (len > 0) {  // the chunk's first stage, peeled: its A, B (c) go on to phase 4
           StageData<NX, NU> st;
           stage3(start, st);
-          riccati_stage(start, st);
+          riccati_stage(start, st, len == 1);
           hA = st.A;
           hB = st.B;
           if constexpr (AFF) hc = st.c; else set_zero(hc);
@@ -918,7 +956,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         for (int s = start + len - 1; s >= start; --s) {
           StageData<NX, NU> st;
           stage3(s, st);
-          riccati_stage(s, st);
+          riccati_stage(s, st, s == sfirst);
         }
       }
     }
@@ -968,11 +1006,11 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
       Mat<NX, NX> Pn;
       NOC_UNROLL for (int i = 0; i < NX; ++i) {
         double t = phi[i];
-        NOC_UNROLL for (int k = 0; k < NX; ++k) t += Phi(i, k) * f[k];
+        NOC_UNROLL for (int k = 0; k < NX; ++k) if (AFF || ST::nzf(k)) t += Phi(i, k) * f[k];
         phi[i] = t;
         NOC_UNROLL for (int j = 0; j < NX; ++j) {
           double u = 0.0;
-          NOC_UNROLL for (int k = 0; k < NX; ++k) u += Phi(i, k) * F(k, j);
+          NOC_UNROLL for (int k = 0; k < NX; ++k) if (ST::nzF(k, j)) u += Phi(i, k) * F(k, j);
           Pn(i, j) = u;
         }
       }
@@ -1176,8 +1214,8 @@ template <int NX, int NU, int L, bool AFF, bool TILED, int CACHE = 0, bool HANDO
 NOC_DEV void kkt_scan_wave(const KKTArgs& a, const int traj, const int l) {
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const ArgsSrc<NX, NU, L, AFF, TILED> src{a, traj, l, cmax, (size_t)traj * a.N};
-  kkt_scan_wave_src<NX, NU, L, AFF, TILED, ArgsSrc<NX, NU, L, AFF, TILED>, CACHE, HANDOFF, BIG, NT3>(a, traj,
-                                                                                               l, src);
+  kkt_scan_wave_src<NX, NU, L, AFF, TILED, ArgsSrc<NX, NU, L, AFF, TILED>, CACHE, HANDOFF, BIG, NT3,
+                    (BIG && ab_supported<NX, NU>()), false, true>(a, traj, l, src);
 }
 
 // BIG (L = 32, 64; nx = 3, 4): one wave per SIMD -- for batches whose waves all fit one per SIMD
