@@ -1,7 +1,13 @@
 """GPU parity of the reference's public building blocks (noc.par_interior_point_newton,
 noc.seq_interior_point_newton, noc.costates) against the oracle restatement (oracle/noc_oracle.py,
 torch.func autodiff).  Tolerances (fp64): derivatives / costates / LQ blocks 1e-10 relative;
-KKT steps 1e-10; one-stage Newton loops identical iteration counts, iterates 1e-6."""
+KKT steps 1e-10; one-stage Newton loops identical iteration counts, iterates 1e-6.
+
+The shapes here are small (B <= 3, N <= 40, nu = 1, B * N <= 111): they pin the API and the
+families' derivatives, not the kernels' loops.  With N < 64 every lane of the parallel costate scan
+owns at most one stage, noc_lqr_params runs with nu = 1 only and no launch reaches a second block;
+tests/test_blocks_dense_gpu.py covers those paths (dense data, nx = 1..8, nu up to 8, N up to 200,
+block crossings)."""
 import numpy as np
 import pytest
 
