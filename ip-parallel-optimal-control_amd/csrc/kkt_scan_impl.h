@@ -323,9 +323,11 @@ NOC_DEV void prepend(Elem<NX>& e, const StageData<NX, NU>& st, double reg) {
 // so the result is value-only too and only J, nu are formed (T A1 is the only solve needed); A, b,
 // C are zeroed in every lane.
 // T = (I + C1 J2)^-1: nx = 2 in closed form (one division; det(I + C1 J2) >= 1 for C1, J2 >= 0);
-// larger nx by threshold-checked Gaussian elimination without row exchanges, redone with partial
-// pivoting by the whole segment (uniform branch, so the re-fetch is legal) if any lane's check
-// fails.
+// larger nx by threshold-checked Gaussian elimination without row exchanges, redone with threshold
+// pivoting by the whole WAVE (uniform branch, so the re-fetch is legal) if any lane's check fails.
+// The vote spans the wave, which at L < 64 holds other trajectories too: the redone solve gives a
+// lane whose own check passed the bits it already had (lu_pp_solve exchanges no row for it), so a
+// trajectory's result does not depend on its wave-mates (tests/test_kkt_neighbours_gpu.py).
 template <int NX, bool VALUE_ONLY, int SK, bool MASKED = (NX <= 2)>
 NOC_DEV void combine_sklansky(Elem<NX>& e1) {
   const int lane = (int)__lane_id();
@@ -388,7 +390,7 @@ NOC_DEV void combine_sklansky(Elem<NX>& e1) {
     else ok = lu_np_solve<NX, NR>(X, Y);
   }
   if constexpr (NX != 2) {
-    if (__any(!ok)) {  // uniform over the segment: J2 / nu2 re-fetched instead of kept live
+    if (__any(!ok)) {  // uniform over the wave: J2 / nu2 re-fetched instead of kept live
       fetch_value();
       if (act) {
         build();

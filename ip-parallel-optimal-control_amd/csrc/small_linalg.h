@@ -480,8 +480,10 @@ NOC_DEV bool ldl_solve(const Sym<N>& W, double (&Y)[N][NR]) {
 // Gaussian elimination WITHOUT row exchanges, accepted only if every pivot passes the
 // threshold-pivoting test |p_k| >= tau * max_{i>=k} |x_ik| (tau = 1/2 bounds element growth like
 // partial pivoting does, within a factor (1+1/tau)^(N-1)).  Returns false (X, Y garbage) if a
-// pivot fails; the caller then redoes the solve with lu_pp_solve.  No selects: ~1/3 fewer VALU
-// instructions than the pivoting solve.
+// pivot fails; the caller then redoes the solve with lu_pp_solve, which pivots by the same
+// threshold: on a matrix that passes here it repeats this function's operations bit for bit
+// (tests/test_kkt_neighbours_gpu.py).  No selects: ~1/3 fewer VALU instructions than the
+// pivoting solve.
 template <int N, int NR>
 NOC_DEV bool lu_np_solve(double (&X)[N][N], double (&Y)[N][NR]) {
   bool ok = true;
@@ -507,8 +509,14 @@ NOC_DEV bool lu_np_solve(double (&X)[N][N], double (&Y)[N][NR]) {
   return ok;
 }
 
-// Gaussian elimination with partial pivoting (row swaps as selects, so everything stays in
-// VGPRs).  X (N x N) is destroyed; Y (N x NR) becomes X^{-1} Y.
+// Gaussian elimination with THRESHOLD pivoting, the same tau = 1/2 as lu_np_solve's test: step k
+// keeps the diagonal if |x_kk| >= tau * colmax and exchanges it with the (first) largest row
+// otherwise (row swaps as selects, so everything stays in VGPRs).  A matrix whose every pivot
+// passes lu_np_solve's test therefore sees no exchange and runs lu_np_solve's own operation
+// sequence -- the same bits -- so a lane that is sent here only because ANOTHER lane of its wave
+// failed the test (combine_sklansky's wave-wide vote) gets the result it already had.  Element
+// growth is bounded as documented there ((1 + 1/tau)^(N-1)).  X (N x N) is destroyed; Y (N x NR)
+// becomes X^{-1} Y.
 template <int N, int NR>
 NOC_DEV void lu_pp_solve(double (&X)[N][N], double (&Y)[N][NR]) {
   NOC_UNROLL for (int k = 0; k < N; ++k) {
@@ -521,6 +529,7 @@ NOC_DEV void lu_pp_solve(double (&X)[N][N], double (&Y)[N][NR]) {
         best = better ? a : best;
         piv = better ? i : piv;
       }
+      piv = (fabs(X[k][k]) >= 0.5 * best) ? k : piv;  // lu_np_solve's accept test: no exchange
       NOC_UNROLL for (int i = k + 1; i < N; ++i) {
         const bool sw = (piv == i);
         NOC_UNROLL for (int j = k; j < N; ++j) {

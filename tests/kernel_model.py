@@ -58,6 +58,87 @@ def combine(e1, e2):
     return (A, b, 0.5 * (C + C.T), nu, 0.5 * (J + J.T))
 
 
+def lu_np_ok(X, tau=0.5):
+    """The accept test of the device's elimination without row exchanges (small_linalg.h
+    lu_np_solve), step for step: every pivot must satisfy |x_kk| >= tau * max_{i>=k} |x_ik| on the
+    matrix eliminated so far.  tau = 0.5 is the device's; the case scans use other values to keep
+    a margin from the threshold."""
+    X = np.array(X, dtype=np.float64)
+    n = X.shape[0]
+    for k in range(n):
+        colmax = np.max(np.abs(X[k:, k]))
+        if not (abs(X[k, k]) >= tau * colmax and colmax > 0.0):
+            return False
+        inv = 1.0 / X[k, k]
+        for i in range(k + 1, n):
+            X[i, k + 1:] -= (X[i, k] * inv) * X[k, k + 1:]
+    return True
+
+
+def pp_would_swap(X, ratio=1.0):
+    """True if elimination with partial pivoting (the first largest |x_ik|, i >= k, as
+    small_linalg.h lu_pp_solve picks it) exchanges rows at any step.  ratio > 1 asks for the
+    off-diagonal entry to beat the diagonal by that factor (a margin for the case scans)."""
+    X = np.array(X, dtype=np.float64)
+    n = X.shape[0]
+    swapped = False
+    for k in range(n):
+        piv, best = k, abs(X[k, k])
+        for i in range(k + 1, n):
+            if abs(X[i, k]) > best:
+                piv, best = i, abs(X[i, k])
+        if piv != k:
+            swapped = swapped or best > ratio * abs(X[k, k])
+            X[[k, piv]] = X[[piv, k]]
+        inv = 1.0 / X[k, k]
+        for i in range(k + 1, n):
+            X[i, k + 1:] -= (X[i, k] * inv) * X[k, k + 1:]
+    return swapped
+
+
+def phase2_pivot_census(A, B, Q, R, M, r, P, reg=0.0, q=None, c=None, p=None, L=64, tau=0.5,
+                        ratio=1.0):
+    """Walks the device's phase-2 tree (kkt_scan_impl.h rev_scan_sklansky) of ONE trajectory over an
+    L-lane segment (L <= 64, a power of two) and classifies every combine's X = I + C1 J2.
+    Chunks as chunk_bounds, the last lane seeded with (P, p); at distance d the lanes with bit d
+    clear combine with the first lane of the upper half of their aligned 2d-lane block.
+    Returns one (failing, passing_but_swapped) pair of counts per level: combines that fail
+    lu_np_ok(X, tau), and combines that pass it although pp_would_swap(X, ratio)."""
+    N, nx, nu = B.shape
+    q = np.zeros((N, nx)) if q is None else q
+    c = np.zeros((N, nx)) if c is None else c
+    p = np.zeros(nx) if p is None else p
+    Rr = R + reg * np.eye(nu)
+    starts, lens = chunk_bounds(N, L)
+    cur = []
+    for l in range(L):
+        if l == L - 1:
+            acc = (np.zeros((nx, nx)), np.zeros(nx), np.zeros((nx, nx)), p.copy(), P.copy())
+        else:
+            acc = (np.eye(nx), np.zeros(nx), np.zeros((nx, nx)), np.zeros(nx), np.zeros((nx, nx)))
+        for s in range(starts[l] + lens[l] - 1, starts[l] - 1, -1):
+            acc = prepend(acc, A[s], B[s], Q[s], Rr[s], M[s], r[s], q[s], c[s])
+        cur.append(acc)
+    levels = []
+    d = 1
+    while d < L:
+        nxt = list(cur)
+        fails = swaps = 0
+        for l in range(L):
+            if l & d:
+                continue
+            e2 = cur[(l & ~(2 * d - 1)) + d]
+            X = np.eye(nx) + cur[l][2] @ e2[4]
+            if not lu_np_ok(X, tau):
+                fails += 1
+            elif pp_would_swap(X, ratio):
+                swaps += 1
+            nxt[l] = combine(cur[l], e2)
+        levels.append((fails, swaps))
+        cur, d = nxt, d * 2
+    return levels
+
+
 def model_kkt(A, B, Q, R, M, r, P, reg=0.0, x0=None, q=None, c=None, p=None, L=64):
     N, nx, nu = B.shape
     q = np.zeros((N, nx)) if q is None else q
