@@ -21,6 +21,16 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b)) / max(1.0, float(np.max(np.abs(b)))))
 
 
+def _rel_own(a, b):
+    """relative to the field's own maximum, no floor of 1: fu and fxu are ~1e-3 at these step
+    sizes, and a floor of 1 would hide a relative error a thousand times the tolerance (an
+    identically zero reference demands exact zeros)"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    scale = float(np.max(np.abs(b)))
+    diff = float(np.max(np.abs(a - b)))
+    return diff / scale if scale > 0.0 else (0.0 if diff == 0.0 else np.inf)
+
+
 def _case(name, N, B, seed):
     from noc import problems
     from oracle import noc_oracle as O, problems as PR
@@ -57,7 +67,7 @@ def test_derivatives_costates_lqr_params(name):
     for b in range(B):
         ref = prob.derivatives(X[b], u0[b], bp[b])
         for k, r in zip(d._fields, ref):
-            assert _rel(getattr(d, k)[b].cpu(), r) < 1e-10, k
+            assert _rel_own(getattr(d, k)[b].cpu(), r) < 1e-10, k
         lamT, _ = prob.final_grad_hess(X[b, -1])
         lam = O.seq_costates(lamT, ref[0], ref[5])
         assert _rel(ls[b].cpu(), lam) < 1e-12 and _rel(lp[b].cpu(), lam) < 1e-10
