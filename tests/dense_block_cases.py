@@ -145,8 +145,9 @@ def ddp_bwd_ld(Vx_T, Vxx_T, derivs, reg_param, quu="full", info=None, dtype=LD):
     quu="full": the reference's statements; quu="upper": Quu mirrored from its upper triangle before
     the eigenvalue test and the solves (the contract of noc_ddp_bwd_pass).  info (a dict) receives
     min_eig, the smallest eigenvalue of any stage's Quu as solved (fp64 eigvalsh of the cast), and
-    max_Vxx, max_Vx, the largest magnitudes along the recursion.  dtype=np.float64 runs the very
-    same statements in fp64 (the recipe test measures the recursion's conditioning with it)."""
+    max_Vxx, max_Vx, max_Quu, the largest magnitudes along the recursion.  dtype=np.float64 runs
+    the very same statements in fp64 (the recipe test measures the recursion's conditioning with
+    it)."""
     LD = dtype
     cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu = (np.asarray(a, LD) for a in derivs)
     N, nu = cu.shape
@@ -155,7 +156,7 @@ def ddp_bwd_ld(Vx_T, Vxx_T, derivs, reg_param, quu="full", info=None, dtype=LD):
     Vx, Vxx = np.asarray(Vx_T, LD), np.asarray(Vxx_T, LD)
     k, K, Hu = np.zeros((N, nu), LD), np.zeros((N, nu, nx), LD), np.zeros((N, nu), LD)
     dV = np.zeros(N, LD)
-    feasible, min_eig, max_Vxx, max_Vx = True, np.inf, 0.0, 0.0
+    feasible, min_eig, max_Vxx, max_Vx, max_Quu = True, np.inf, 0.0, 0.0, 0.0
     for t in range(N - 1, -1, -1):
         Qx = cx[t] + fx[t].T @ Vx                                        # D:41
         Qu = cu[t] + fu[t].T @ Vx                                        # D:42
@@ -169,7 +170,8 @@ def ddp_bwd_ld(Vx_T, Vxx_T, derivs, reg_param, quu="full", info=None, dtype=LD):
             raise ValueError(quu)
         ev = float(np.min(np.linalg.eigvalsh(_sym(Quu.astype(np.float64)))))
         min_eig = min(min_eig, ev)
-        feasible &= ev > 0                                               # D:47-48
+        max_Quu = max(max_Quu, float(np.max(np.abs(Quu))))
+        feasible &= ev > 0                                            # D:47-48
         sol = solve_ld(Quu, np.concatenate([Qu[:, None], Qxu.T], axis=1), LD)
         iQu, iQxuT = sol[:, 0], sol[:, 1:]
         k[t] = -iQu                                                      # D:50
@@ -181,7 +183,7 @@ def ddp_bwd_ld(Vx_T, Vxx_T, derivs, reg_param, quu="full", info=None, dtype=LD):
         max_Vxx = max(max_Vxx, float(np.max(np.abs(Vxx))))
         max_Vx = max(max_Vx, float(np.max(np.abs(Vx))))
     if info is not None:
-        info.update(min_eig=min_eig, max_Vxx=max_Vxx, max_Vx=max_Vx)
+        info.update(min_eig=min_eig, max_Vxx=max_Vxx, max_Vx=max_Vx, max_Quu=max_Quu)
     return k, K, dV.sum(), feasible, Hu                                  # D:61-70
 
 

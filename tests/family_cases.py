@@ -92,7 +92,9 @@ def angle_index(name):
 # the 50-digit reference
 # --------------------------------------------------------------------------------------------------
 def _m(v):
-    return mpf(float(v))
+    """the mpf of an fp64 input; an mpf passes through unrounded (tests/ddp_pass_cases.py hands the
+    stage functions below the states of a 50-digit rollout)"""
+    return v if isinstance(v, mpf) else mpf(float(v))
 
 
 def wrap_mp(a):
