@@ -244,6 +244,10 @@ int noc_ipm_promote(const noc_ipm_ws* ws, void* stream);
 int noc_kkt_compact_supported(const noc_family* fam, int N, int lanes);
 /* doubles per stage of the compact field NOC_FIELD_*; -1 for an unsupported family or field. */
 int noc_compact_width(const noc_family* fam, int field);
+/* chunk slots whose A, B noc_kkt_solve_compact keeps on chip between its backward and forward
+ * passes at (family, lanes) -- a property of the build, for tests and tools; results do not depend
+ * on it.  -1 where noc_kkt_compact_supported is 0. */
+int noc_kkt_compact_keep(const noc_family* fam, int lanes);
 /* noc_kkt_solve_tiled (no q, c, p) on compact A, Bm, Q, R, M: same outputs, same layouts. */
 int noc_kkt_solve_compact(const noc_family* fam, int N, int B, int lanes,
                           const double* A, const double* Bm, const double* Q, const double* R,

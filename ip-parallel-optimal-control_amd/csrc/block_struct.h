@@ -27,16 +27,6 @@
 
 namespace noc {
 
-// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
-template <class F, int... I>
-NOC_DEV void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-NOC_DEV void static_for(F&& f) {
-  static_for_seq(f, std::make_integer_sequence<int, N>{});
-}
-
 // how a block entry is obtained
 enum BlockKind : int {
   BK_VAR = 0,  // stored (depends on x, u, lambda or bp)
@@ -225,6 +215,17 @@ constexpr KindTable<NX * NU> table_M() {
       }
     }
   return t;
+}
+
+// Chunk slots whose compact A, B record the stand-alone compact scan keeps in registers from its
+// phase 3 to its phase 4 (kkt_scan_impl.h: KEEP; noc_kkt_compact_keep), per (family, lanes), from
+// the compiler's resource report.  Cart-pole: 7, a whole chunk of the N = 200,
+// lanes-32 launch (6 doubles per slot); its scratch does not depend on the count (60 B per lane
+// at every count from 1 to 7 against 52 B without the buffer, spilled once around phase 2).
+// Pendulum (1 double per slot): 4, the most that keeps 5 waves per SIMD (94 VGPRs; 8 takes 102).
+constexpr int compact_keep(int kind, int lanes) {
+  (void)lanes;
+  return kind == NOC_FAMILY_CARTPOLE ? 7 : 4;
 }
 
 template <int N>

@@ -87,6 +87,10 @@ int compact_width(const noc_family& p, int field) {
   return -1;
 }
 
+int kkt_compact_keep(const noc_family& p, int lanes) {
+  return kkt_compact_supported(p, lanes) ? compact_keep(p.kind, lanes) : -1;
+}
+
 hipError_t kkt_compact_dispatch(const noc_family& p, const KKTArgs& a, int lanes, hipStream_t stream) {
 #define X(K, NX, NU) if (p.kind == K && p.nx == NX && p.nu == NU) return dispatch_t<K, NX, NU>(p, a, lanes, stream);
   NOC_COMPACT_FAMILIES(X)
@@ -111,6 +115,7 @@ hipError_t blocks_expand(const noc_family& p, const ExpandArgs& e, hipStream_t s
 
 bool kkt_compact_supported(const noc_family&, int) { return false; }
 int compact_width(const noc_family&, int) { return -1; }
+int kkt_compact_keep(const noc_family&, int) { return -1; }
 hipError_t kkt_compact_dispatch(const noc_family&, const KKTArgs&, int, hipStream_t) { return hipErrorInvalidValue; }
 hipError_t blocks_expand(const noc_family&, const ExpandArgs&, hipStream_t) { return hipErrorInvalidValue; }
 

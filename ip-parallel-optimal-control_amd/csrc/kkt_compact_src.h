@@ -59,6 +59,20 @@ struct CompactSrc {
     set_zero(c);
   }
   NOC_DEV void cvec(int, int, Vec<NX>& c) const { set_zero(c); }
+  // The compact A, B record of a stage the scan keeps on chip from phase 3 to phase 4
+  // (kkt_scan_wave_src: KEEP): pack_ab takes the variable entries back out of the expanded blocks,
+  // unpack_ab is ab() on the record instead of on memory -- the same expand, the same doubles.
+  static constexpr int kNvA = BS::template nv<BF_A>(), kNvB = BS::template nv<BF_B>();
+  static constexpr int kRecAB = kNvA + kNvB;
+  NOC_DEV void pack_ab(const Mat<NX, NX>& A, const Mat<NX, NU>& Bm, double* rec) const {
+    BS::template compress<BF_A>(A.v, rec);
+    BS::template compress<BF_B>(Bm.v, rec + kNvA);
+  }
+  NOC_DEV void unpack_ab(const double* rec, Mat<NX, NX>& A, Mat<NX, NU>& Bm, Vec<NX>& c) const {
+    BS::template expand<BF_A>(p, rec, A.v);
+    BS::template expand<BF_B>(p, rec + kNvA, Bm.v);
+    set_zero(c);
+  }
 };
 
 // The stand-alone scan on compact blocks: kkt_scan_kernel's tiled, non-affine instance with the
@@ -66,7 +80,7 @@ struct CompactSrc {
 // barrier prologue, same register budgets (BIG: one wave per SIMD); no A, B slots in LDS and no
 // non-temporal phase-3 instance (the compact blocks of the batches those exist for stay within the
 // memory-side cache).
-template <int KIND, int NX, int NU, int L, int CACHE, bool BIG>
+template <int KIND, int NX, int NU, int L, int CACHE, bool BIG, int KEEP = 0>
 __global__ __launch_bounds__(256, BIG ? 1 : NOC_KKT_WAVES_PER_SIMD) void kkt_scan_compact_kernel(noc_family prm,
                                                                                              KKTArgs a) {
   static_assert(L <= 64, "one-wave segments");
@@ -85,7 +99,7 @@ __global__ __launch_bounds__(256, BIG ? 1 : NOC_KKT_WAVES_PER_SIMD) void kkt_sca
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const CompactSrc<BS, NX, NU, L> src{a, prm, traj, l, cmax, (size_t)traj * a.N};
   kkt_scan_wave_src<NX, NU, L, false, true, CompactSrc<BS, NX, NU, L>, CACHE, true, BIG, false, false, false,
-                    true>(a, traj, l, src);  // ..., no NT3, no AB, no IO0, PEEL
+                    true, KEEP>(a, traj, l, src);  // ..., no NT3, no AB, no IO0, PEEL, KEEP
 }
 
 // launch_kkt's geometry (LDS slots, waves per workgroup, the one-wave-per-SIMD instance when every
@@ -99,6 +113,7 @@ hipError_t launch_kkt_compact(const noc_family& prm, const KKTArgs& a_in, hipStr
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const bool cached = CC > 0 && cmax <= CC && !(a.ablate & 8);
   constexpr bool kHasBig = (L == 64 || L == 32) && NX >= 3 && NX <= 4;
+  constexpr int KP = compact_keep(KIND, L);  // the streamed instances' kept slots (block_struct.h)
   const bool big = kHasBig && (threads + 63) / 64 <= kkt_device_simds() && kkt_big_enabled();
   const size_t slots1 = (a.mode == MODE_BWD || (!a.dx && !a.du)) ? 0 : kkt_lds_bytes_rt(NX, NU, a.N, L);
   const int wpb = kkt_waves_per_block((threads + 63) / 64, slots1);
@@ -116,10 +131,10 @@ hipError_t launch_kkt_compact(const noc_family& prm, const KKTArgs& a_in, hipStr
                          prm, a);
   } else if (big) {
     if constexpr (kHasBig)
-      hipLaunchKernelGGL((kkt_scan_compact_kernel<KIND, NX, NU, L, 0, true>), dim3(grid), dim3(block), lds, stream,
+      hipLaunchKernelGGL((kkt_scan_compact_kernel<KIND, NX, NU, L, 0, true, KP>), dim3(grid), dim3(block), lds, stream,
                          prm, a);
   } else {
-    hipLaunchKernelGGL((kkt_scan_compact_kernel<KIND, NX, NU, L, 0, false>), dim3(grid), dim3(block), lds, stream,
+    hipLaunchKernelGGL((kkt_scan_compact_kernel<KIND, NX, NU, L, 0, false, KP>), dim3(grid), dim3(block), lds, stream,
                        prm, a);
   }
   return hipGetLastError();

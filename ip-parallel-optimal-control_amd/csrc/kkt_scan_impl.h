@@ -609,6 +609,14 @@ struct ArgsSrc {
   }
 };
 
+// doubles of one kept A, B record (kkt_scan_wave_src: KEEP); sources without a compact record
+// (ArgsSrc) are only ever asked with KEEP = 0
+template <class SRC, int KEEP>
+constexpr int keep_rec_doubles() {
+  if constexpr (KEEP > 0) return SRC::kRecAB > 0 ? SRC::kRecAB : 1;
+  else return 1;
+}
+
 // The whole KKT solve of trajectory `traj` by lane `l` of its L-lane segment (the kernel below;
 // also called by the persistent interior-point solver, ipm_persistent.hip).  With lds_out set and
 // dx = du = NULL the step stays in the LDS slots (x_s at slot s, u_s after it, x_N at slot N).
@@ -632,12 +640,23 @@ struct ArgsSrc {
 // Off inside the persistent solvers: the extra copy of the stage costs their instances registers
 // (pendulum 158 -> 168-170 VGPRs and 3 -> 2 waves per SIMD, cart-pole two-wave 352 -> 376-448 B of
 // scratch, compiler's resource report) for 8-56 FMAs per chunk.
+// KEEP > 0 (the stand-alone compact scan, kkt_compact_src.h; needs PEEL, no CACHE, no AB, no affine
+// term): the hand-off widened to the chunk's first KEEP slots.  Phase 3 keeps the compact A, B
+// record (SRC::pack_ab: the variable entries, SRC::kRecAB doubles) of every slot j < KEEP in a
+// register buffer, phase 4 expands them again (SRC::unpack_ab: the doubles the re-read's expand
+// gives) and re-reads only the slots j >= KEEP, the first of them issued before the forward scan,
+// which it does not depend on.  Phase 3's loop then runs over the wave-uniform slot (lanes with the
+// shorter chunk sit out its first pass instead of its last), so the buffer is indexed by a scalar
+// and stays in registers.  Off (0) everywhere else: the one-stage hand-off above.
 template <int NX, int NU, int L, bool AFF, bool TILED, class SRC, int CACHE = 0, bool HANDOFF = true,
           bool BIG = false, bool NT3 = false, bool AB = (BIG && ab_supported<NX, NU>()), bool IO0 = false,
-          bool PEEL = false>
+          bool PEEL = false, int KEEP = 0>
 NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, const SRC& src) {
   constexpr int KD = kd_width<NX, NU>();
   using ST = typename SRC::Struct;  // structural zeros of A, B (DenseBlocks: none)
+  static_assert(KEEP == 0 || (PEEL && HANDOFF && CACHE == 0 && !AB && !AFF && L <= 64),
+                "KEEP: the streamed, non-affine one-wave hand-off path with the peeled first stage");
+  constexpr int REC = keep_rec_doubles<SRC, KEEP>();
   if (traj >= a.B) return;                     // uniform over the segment
   if (a.active && a.active[traj] == 0) return;  // uniform over the segment
   const int N = a.N;
@@ -687,6 +706,21 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   Mat<NX, NU> hB;
   Vec<NX> hc;
   bool handed = false;
+  // KEEP: the compact A, B records of chunk slots j < KEEP, phase 3 -> phase 4.  Every access has a
+  // compile-time slot (NOC_KEEP_PUT's unrolled compare, phase 4's unrolled slots), so the array is
+  // promoted to registers; a slot is read only where phase 3 wrote it (j < len).  The store is a
+  // macro, not a lambda: a lambda's body is optimised on its own first, where kbuf is a pointer,
+  // and its chain of compares is folded into one store to kbuf[j] -- scratch memory.
+  double kbuf[KEEP > 0 ? KEEP : 1][REC];
+  (void)kbuf;
+#define NOC_KEEP_PUT(J, STAGE)                                                        \
+  do {                                                                                \
+    double rec_[REC];                                                                 \
+    src.pack_ab((STAGE).A, (STAGE).B, rec_);                                          \
+    NOC_UNROLL for (int k_ = 0; k_ < KEEP; ++k_) {                                    \
+      if ((J) == k_) { NOC_UNROLL for (int i_ = 0; i_ < REC; ++i_) kbuf[k_][i_] = rec_[i_]; } \
+    }                                                                                 \
+  } while (0)
   // ablation bit 4 (timing only, results wrong): phases 3 and 4 re-read the blocks of trajectory
   // traj & 1 instead of their own -- an L2-resident working set, so the time they lose against
   // the full kernel is the cost of re-reading the blocks from beyond L2
@@ -930,6 +964,31 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
             riccati_stage(s, st, s == sfirst);
           }
         }
+      } else if constexpr (KEEP > 0) {
+        // As the hand-off path below, with the stages between the two peeled ones run by slot: pass
+        // jj runs slot jj of every lane that still has it (the lanes whose chunk is one stage
+        // shorter took slot cmax - 2 as their first stage and sit out pass cmax - 2), so the slot
+        // is a scalar and NOC_KEEP_PUT's compare a scalar branch.  Same stages, same order per lane.
+        if (len > 1) {  // the first executed stage: slot len - 1 (two values across the wave)
+          StageData<NX, NU> st;
+          stage3(sfirst, st);
+          riccati_stage(sfirst, st, kFirst);
+          NOC_KEEP_PUT(len - 1, st);
+        }
+        for (int jj = cmax - 2; jj >= 1; --jj) {
+          if (jj <= len - 2) {
+            StageData<NX, NU> st;
+            stage3(start + jj, st);
+            riccati_stage(start + jj, st, kLater);
+            NOC_KEEP_PUT(jj, st);
+          }
+        }
+        if (len > 0) {
+          StageData<NX, NU> st;
+          stage3(start, st);
+          riccati_stage(start, st, len == 1);
+          NOC_KEEP_PUT(0, st);  // (phase 4 takes the kept slots under the hand-off's condition: `kept`)
+        }
       } else if constexpr (HANDOFF) {
         // the first executed stage peeled too (Phi = F, phi = f: riccati_stage): every lane with
         // more than one stage takes it in the same iteration, so the wave does not diverge
@@ -1032,6 +1091,21 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     }
     set_zero(Phi);
   }
+  // KEEP: A, B of the first slot the propagation still has to read (slot `kept`, where the chunk
+  // is longer than the buffer) do not depend on the scan: issued here, so the scan covers the load
+  Mat<NX, NX> pA;
+  Mat<NX, NU> pB;
+  Vec<NX> pc;
+  // chunk slots phase 4 takes from kbuf (wave-uniform; the condition `handed` was set under)
+  const int kept = (KEEP > 0 && a.mode == MODE_FULL && !(a.ablate & 32)) ? KEEP : 0;
+  bool pre = false;
+  if constexpr (KEEP > 0) {
+    if (len > kept) {
+      src_re.ab(start + kept, kept, pA, pB, pc);
+      pre = true;
+    }
+  }
+  (void)kept;
   affine_prefix_sklansky<NX, LW>(Phi, phi);  // partners on the VALU (small_linalg.h)
   Vec<NX> x;
   wave_shift_up1<NX>(phi.v, x.v);  // lane l-1's prefix; segment starts: x0 / the join below
@@ -1144,10 +1218,44 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         s0 = start + jl;
       }
     }
+    // KEEP: the chunk's first `kept` slots with A, B expanded from phase 3's records
+    if constexpr (KEEP > 0) {
+      if (kept > 0) {
+        static_for<KEEP>([&](auto KC) {
+          constexpr int k = decltype(KC)::value;
+          if (k < len) {
+            const int s = start + k;
+            Mat<NX, NX> A;
+            Mat<NX, NU> Bm;
+            Vec<NX> cc;
+            double rec[REC];
+            static_for<REC>([&](auto IC) { rec[decltype(IC)::value] = kbuf[k][decltype(IC)::value]; });
+            src.unpack_ab(rec, A, Bm, cc);
+            double Kk[NU * (NX + 1)];
+            if (kd_lds) {
+              NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) Kk[i] = slot[s * KD + i];
+            } else {
+              load_Kd<NX, NU, L, TILED>(a, traj, tN + s, k, l, cmax, Kk);
+            }
+            fwd_stage(s, A, Bm, cc, Kk);
+          }
+        });
+        s0 = start + (len < KEEP ? len : KEEP);
+      }
+    }
     // one stage prefetched (a two-deep prefetch measured no faster: the propagation runs at the
     // rate the A, B re-reads stream at, not at the per-stage latency)
     if (s0 < start + len) {
-      if (handed && s0 == start) {  // stage `start` from phase 3's registers; only its K, d from LDS
+      if (pre) {  // KEEP: stage s0's A, B were issued before the forward scan; only its K, d here
+        nA = pA;
+        nB = pB;
+        nc = pc;
+        if (kd_lds) {
+          NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) nK[i] = slot[s0 * KD + i];
+        } else {
+          load_Kd<NX, NU, L, TILED>(a, traj, tN + s0, s0 - start, l, cmax, nK);
+        }
+      } else if (handed && s0 == start) {  // stage `start` from phase 3's registers; only its K, d from LDS
         nA = hA;
         nB = hB;
         nc = hc;
@@ -1209,6 +1317,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     }
   }
   NOC_STAMP(6);
+#undef NOC_KEEP_PUT
 }
 
 template <int NX, int NU, int L, bool AFF, bool TILED, int CACHE = 0, bool HANDOFF = true,

@@ -219,6 +219,11 @@ int noc_compact_width(const noc_family* fam, int field) {
   return w < 0 ? fail(-1, "noc_compact_width: unsupported family or field") : w;
 }
 
+int noc_kkt_compact_keep(const noc_family* fam, int lanes) {
+  if (!fam) return fail(-1, "family is NULL");
+  return noc::kkt_compact_keep(*fam, lanes);
+}
+
 // family / dims / lanes of the compact entry points (before any HIP call)
 static int check_compact_dims(const noc_family* fam, int N, int B, int lanes) {
   if (!fam) return fail(-1, "family is NULL");

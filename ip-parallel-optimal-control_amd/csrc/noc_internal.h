@@ -217,6 +217,7 @@ bool kkt_supported(int nx, int nu);
 // generated families, one-wave segments.  field: BF_A .. BF_M (block_struct.h)
 bool kkt_compact_supported(const noc_family& p, int lanes);
 int compact_width(const noc_family& p, int field);
+int kkt_compact_keep(const noc_family& p, int lanes);  // -1: no compact scan at (family, lanes)
 hipError_t kkt_compact_dispatch(const noc_family& p, const KKTArgs& a, int lanes, hipStream_t stream);
 // dense tiled A, B, Q, R, M <- the compact fields + the family's constants
 struct ExpandArgs {

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 namespace noc {
 
 #define NOC_DEV __device__ __forceinline__
@@ -18,6 +20,16 @@ namespace noc {
 #else
 #define NOC_ISA_MARK(tag, k) do { } while (0)
 #endif
+
+// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
+template <class F, int... I>
+NOC_DEV void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+NOC_DEV void static_for(F&& f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
 
 template <int R, int C>
 struct Mat {

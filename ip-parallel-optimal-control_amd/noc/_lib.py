@@ -104,6 +104,7 @@ SIGNATURES.update({
     "noc_ipm_promote": (_i, [_wp, _dp]),
     "noc_kkt_compact_supported": (_i, [_fp, _i, _i]),
     "noc_compact_width": (_i, [_fp, _i]),
+    "noc_kkt_compact_keep": (_i, [_fp, _i]),
     "noc_kkt_solve_compact": (_i, [_fp, _i, _i, _i] + [_dp] * 10 + [_dp] * 8 + [_dp]),
     "noc_blocks_expand": (_i, [_fp, _i, _i, _i] + [_dp] * 10 + [_dp]),
     "noc_ipm_prepare_compact": (_i, [_fp, _wp, _i, _i, _dp]),
