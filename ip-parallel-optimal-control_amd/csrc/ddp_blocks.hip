@@ -156,15 +156,11 @@ __global__ __launch_bounds__(64) void nonlin_rollout_kernel(noc_family prm, int 
 
 hipError_t nonlin_rollout(const noc_family& p, int N, int B, const double* K, const double* k,
                           const double* x, const double* u, double* xn, double* un, hipStream_t s) {
-#define NOC_FAMILY(KD, X, U)                                                                    \
-  if (p.kind == KD && p.nx == X && p.nu == U) {                                                 \
-    hipLaunchKernelGGL((nonlin_rollout_kernel<KD, X, U>), dim3((B + 63) / 64), dim3(64), 0, s, p, \
-                       N, B, K, k, x, u, xn, un);                                               \
-    return hipGetLastError();                                                                   \
-  }
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return for_family(p, hipErrorInvalidValue, [&](auto KD, auto X, auto U) {
+    hipLaunchKernelGGL((nonlin_rollout_kernel<KD, X, U>), dim3((B + 63) / 64), dim3(64), 0, s, p, N, B, K,
+                       k, x, u, xn, un);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace noc

@@ -15,120 +15,126 @@
 
 namespace noc {
 
+// Per-trajectory cost parameters (the noc_*_params building blocks): the kernels below that read a
+// cost parameter take the records tp (Bt, NOC_TRAJ_PARAM_DOUBLES) as a trailing argument pack
+// (ipm_family.h: TrajParams, load_traj_params) -- empty in the shared-parameter instance.  With
+// it, the family argument first takes trajectory b's goal, wx, wu, wf, u_bound from its record,
+// behind the kernel's own in-range test of b.  Such instances exist for the families with the
+// parametrised cost only (traj_params_instance).
+
 // one thread per (trajectory, stage)
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void derivatives_kernel(noc_family prm, DerivArgs a) {
-#include "deriv_body_derivatives.h"
+template <int KIND, int NX, int NU, class... TP>
+__global__ __launch_bounds__(256) void derivatives_kernel(noc_family prm, DerivArgs a, TP... tp) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)a.B * a.N) return;
+  const int N = a.N;
+  const long long b = t / N;
+  const size_t bk = (size_t)t;  // b * N + k
+  const int k = (int)(t - b * N);
+  if constexpr (sizeof...(TP) > 0) load_traj_params<NX, NU>(prm, tp..., (int)b);  // b per thread: vector loads
+  Fam<KIND, NX, NU> f(prm);
+  double x[NX], u[NU];
+  NOC_UNROLL for (int i = 0; i < NX; ++i) x[i] = a.x[((size_t)b * (N + 1) + k) * NX + i];
+  NOC_UNROLL for (int j = 0; j < NU; ++j) u[j] = a.u[bk * NU + j];
+  const double bp = a.bp[b];
+  double cx[NX], cu[NU];
+  f.stage_grad(x, u, bp, cx, cu);
+  NOC_UNROLL for (int i = 0; i < NX; ++i) a.cx[bk * NX + i] = cx[i];
+  NOC_UNROLL for (int j = 0; j < NU; ++j) a.cu[bk * NU + j] = cu[j];
+  // cxx, cuu, cxu: the stage cost's Hessian (ipm_family.h: stage_hess; for the quadratic-plus-
+  // log-barrier cost of PR:40-50 / CR:36-45 diag(wx), diag(wu + barrier), 0 -- the wrapped
+  // coordinate's mod has derivative 1)
+  {
+    double cxx[NX * NX], cuu[NU * NU], cxu[NX * NU];
+    f.stage_hess(x, u, bp, cxx, cuu, cxu);
+    NOC_UNROLL for (int i = 0; i < NX * NX; ++i) a.cxx[bk * NX * NX + i] = cxx[i];
+    NOC_UNROLL for (int i = 0; i < NU * NU; ++i) a.cuu[bk * NU * NU + i] = cuu[i];
+    NOC_UNROLL for (int i = 0; i < NX * NU; ++i) a.cxu[bk * NX * NU + i] = cxu[i];
+  }
+  double fx[NX * NX], fu[NX * NU];
+  f.jac(x, u, fx, fu);
+  NOC_UNROLL for (int i = 0; i < NX * NX; ++i) a.fx[bk * NX * NX + i] = fx[i];
+  NOC_UNROLL for (int i = 0; i < NX * NU; ++i) a.fu[bk * NX * NU + i] = fu[i];
+  // fxx[i] = d2 f_i / dx dx etc. (jacrev(jacrev(dynamics)) shapes (nx, nx, nx), (nx, nu, nu),
+  // (nx, nx, nu)): the lambda-contracted Hessian at lambda = e_i
+  NOC_UNROLL for (int i = 0; i < NX; ++i) {
+    double l[NX], Hxx[NX * NX], Huu[NU * NU], Hxu[NX * NU];
+    NOC_UNROLL for (int m = 0; m < NX; ++m) l[m] = (m == i) ? 1.0 : 0.0;
+    NOC_UNROLL for (int m = 0; m < NX * NX; ++m) Hxx[m] = 0.0;
+    NOC_UNROLL for (int m = 0; m < NU * NU; ++m) Huu[m] = 0.0;
+    NOC_UNROLL for (int m = 0; m < NX * NU; ++m) Hxu[m] = 0.0;
+    f.add_hess_l(x, u, l, Hxx, Huu, Hxu);
+    NOC_UNROLL for (int m = 0; m < NX * NX; ++m) a.fxx[(bk * NX + i) * NX * NX + m] = Hxx[m];
+    NOC_UNROLL for (int m = 0; m < NU * NU; ++m) a.fuu[(bk * NX + i) * NU * NU + m] = Huu[m];
+    NOC_UNROLL for (int m = 0; m < NX * NU; ++m) a.fxu[(bk * NX + i) * NX * NU + m] = Hxu[m];
+  }
 }
 
 // grad / hessian of final_cost at x_N (one thread per trajectory)
-template <int KIND, int NX, int NU>
+template <int KIND, int NX, int NU, class... TP>
 __global__ __launch_bounds__(256) void final_derivs_kernel(noc_family prm, int B, const double* xN,
-                                                           double* grad, double* hess) {
-#include "deriv_body_final.h"
-}
-
-// Per-trajectory cost parameters (the noc_*_params building blocks): each twin runs its kernel's
-// body on a family argument that first takes trajectory b's goal, wx, wu, wf, u_bound from its
-// record in tp (Bt, NOC_TRAJ_PARAM_DOUBLES) (ipm_family.h: load_traj_params), behind its own
-// in-range test of b.  Instances exist for the families with the parametrised cost only.
-template <int KIND, int NX, int NU>
-constexpr bool block_params_instance() { return !Fam<KIND, NX, NU>::kGenCost; }
-
-// b = t / N per thread: the fields come as vector loads of the trajectory's 256-byte record
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void derivatives_params_kernel(noc_family prm, DerivArgs a,
-                                                                const double* __restrict__ tp) {
-  {
-    const long long tt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tt >= (long long)a.B * a.N) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, (int)(tt / a.N));
-  }
-#include "deriv_body_derivatives.h"
-}
-
-// b per thread
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void final_derivs_params_kernel(noc_family prm, int B, const double* xN,
-                                                                 double* grad, double* hess,
-                                                                 const double* __restrict__ tp) {
-  {
-    const int bt = blockIdx.x * blockDim.x + threadIdx.x;
-    if (bt >= B) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, bt);
-  }
-#include "deriv_body_final.h"
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t derivs_params_family(const noc_family& p, const DerivArgs& a, const double* tp,
-                                       hipStream_t s) {
-  if constexpr (block_params_instance<KIND, NX, NU>()) {
-    const long long n = (long long)a.B * a.N;
-    hipLaunchKernelGGL((derivatives_params_kernel<KIND, NX, NU>), dim3((unsigned)((n + 255) / 256)),
-                       dim3(256), 0, s, p, a, tp);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
+                                                           double* grad, double* hess, TP... tp) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  if constexpr (sizeof...(TP) > 0) load_traj_params<NX, NU>(prm, tp..., b);  // b per thread: vector loads
+  Fam<KIND, NX, NU> f(prm);
+  double x[NX];
+  NOC_UNROLL for (int i = 0; i < NX; ++i) x[i] = xN[(size_t)b * NX + i];
+  double g[NX];
+  f.final_grad(x, g);
+  NOC_UNROLL for (int i = 0; i < NX; ++i) grad[(size_t)b * NX + i] = g[i];
+  if (hess) {
+    double H[NX * NX];
+    f.final_hess(x, H);
+    NOC_UNROLL for (int i = 0; i < NX * NX; ++i) hess[(size_t)b * NX * NX + i] = H[i];
   }
 }
 
-hipError_t derivatives_params(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return derivs_params_family<K, X, U>(p, a, tp, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t final_params_family(const noc_family& p, int B, const double* xN, double* grad,
-                                      double* hess, const double* tp, hipStream_t s) {
-  if constexpr (block_params_instance<KIND, NX, NU>()) {
-    hipLaunchKernelGGL((final_derivs_params_kernel<KIND, NX, NU>), dim3((B + 255) / 256), dim3(256), 0,
-                       s, p, B, xN, grad, hess, tp);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
-hipError_t final_cost_derivs_params(const noc_family& p, int B, const double* xN, double* grad,
-                                    double* hess, const double* tp, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return final_params_family<K, X, U>(p, B, xN, grad, hess, tp, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t derivs_family(const noc_family& p, const DerivArgs& a, hipStream_t s) {
-  const long long n = (long long)a.B * a.N;
-  hipLaunchKernelGGL((derivatives_kernel<KIND, NX, NU>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     s, p, a);
-  return hipGetLastError();
+// tp: nothing, or the records (a TrajParams)
+template <class... TP>
+static hipError_t launch_derivatives(const noc_family& p, const DerivArgs& a, hipStream_t s, TP... tp) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (sizeof...(TP) > 0 && !traj_params_instance<K, X, U>()) {
+      return hipErrorInvalidValue;
+    } else {
+      const long long n = (long long)a.B * a.N;
+      hipLaunchKernelGGL((derivatives_kernel<K, X, U, TP...>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                         s, p, a, tp...);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t derivatives(const noc_family& p, const DerivArgs& a, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return derivs_family<K, X, U>(p, a, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return launch_derivatives(p, a, s);
+}
+
+hipError_t derivatives_params(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s) {
+  return launch_derivatives<TrajParams>(p, a, s, tp);
+}
+
+template <class... TP>
+static hipError_t launch_final_derivs(const noc_family& p, int B, const double* xN, double* grad,
+                                      double* hess, hipStream_t s, TP... tp) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (sizeof...(TP) > 0 && !traj_params_instance<K, X, U>()) {
+      return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((final_derivs_kernel<K, X, U, TP...>), dim3((B + 255) / 256), dim3(256), 0, s, p, B,
+                         xN, grad, hess, tp...);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t final_cost_derivs(const noc_family& p, int B, const double* xN, double* grad,
                              double* hess, hipStream_t s) {
-#define NOC_FAMILY(K, X, U)                                                                     \
-  if (p.kind == K && p.nx == X && p.nu == U) {                                                  \
-    hipLaunchKernelGGL((final_derivs_kernel<K, X, U>), dim3((B + 255) / 256), dim3(256), 0, s, \
-                       p, B, xN, grad, hess);                                                   \
-    return hipGetLastError();                                                                   \
-  }
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return launch_final_derivs(p, B, xN, grad, hess, s);
+}
+
+hipError_t final_cost_derivs_params(const noc_family& p, int B, const double* xN, double* grad,
+                                    double* hess, const double* tp, hipStream_t s) {
+  return launch_final_derivs<TrajParams>(p, B, xN, grad, hess, s, tp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -136,117 +142,98 @@ hipError_t final_cost_derivs(const noc_family& p, int B, const double* xN, doubl
 // over k < N -- the family's whole constraint vector (the u box of the built-ins, a registered
 // family's traced constraints(x, u) incl. state constraints; NaN compares false, as jnp's <= does).
 // One wave64 per trajectory, lanes stride the stages, the verdict is the wave's vote.
-template <int KIND, int NX, int NU>
+template <int KIND, int NX, int NU, class... TP>
 __global__ __launch_bounds__(64) void feasibility_kernel(noc_family prm, int N, int B,
-                                                         const double* x, const double* u, int* ok) {
-#include "deriv_body_feasibility.h"
-}
-
-// per-trajectory cost parameters: one wave per trajectory, so the record index is wave-uniform
-// (scalar loads, the fields stay scalar operands)
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(64) void feasibility_params_kernel(noc_family prm, int N, int B,
-                                                                const double* x, const double* u, int* ok,
-                                                                const double* __restrict__ tp) {
-  {
-    const int bt = blockIdx.x;
-    if (bt >= B) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, bt);
+                                                         const double* x, const double* u, int* ok,
+                                                         TP... tp) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  if constexpr (sizeof...(TP) > 0) load_traj_params<NX, NU>(prm, tp..., b);  // wave-uniform b: scalar loads
+  Fam<KIND, NX, NU> f(prm);
+  bool good = true;
+  for (int k = threadIdx.x; k < N; k += 64) {
+    double xk[NX], uk[NU];
+    NOC_UNROLL for (int i = 0; i < NX; ++i) xk[i] = x[((size_t)b * (N + 1) + k) * NX + i];
+    NOC_UNROLL for (int j = 0; j < NU; ++j) uk[j] = u[((size_t)b * N + k) * NU + j];
+    good = good && f.feasible(xk, uk);
   }
-#include "deriv_body_feasibility.h"
+  const bool all = __all(good);
+  if (threadIdx.x == 0) ok[b] = all ? 1 : 0;
 }
 
-template <int KIND, int NX, int NU>
-static hipError_t feasibility_params_family(const noc_family& p, int N, int B, const double* x,
-                                            const double* u, int* ok, const double* tp, hipStream_t s) {
-  if constexpr (block_params_instance<KIND, NX, NU>()) {
-    hipLaunchKernelGGL((feasibility_params_kernel<KIND, NX, NU>), dim3(B), dim3(64), 0, s, p, N, B, x, u,
-                       ok, tp);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
-hipError_t traj_feasibility_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                                   int* ok, const double* tp, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return feasibility_params_family<K, X, U>(p, N, B, x, u, ok, tp, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+template <class... TP>
+static hipError_t launch_feasibility(const noc_family& p, int N, int B, const double* x, const double* u,
+                                     int* ok, hipStream_t s, TP... tp) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (sizeof...(TP) > 0 && !traj_params_instance<K, X, U>()) {
+      return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((feasibility_kernel<K, X, U, TP...>), dim3(B), dim3(64), 0, s, p, N, B, x, u, ok,
+                         tp...);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t traj_feasibility(const noc_family& p, int N, int B, const double* x, const double* u,
                             int* ok, hipStream_t s) {
-#define NOC_FAMILY(K, X, U)                                                                   \
-  if (p.kind == K && p.nx == X && p.nu == U) {                                                \
-    hipLaunchKernelGGL((feasibility_kernel<K, X, U>), dim3(B), dim3(64), 0, s, p, N, B, x, u, \
-                       ok);                                                                   \
-    return hipGetLastError();                                                                 \
-  }
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return launch_feasibility(p, N, B, x, u, ok, s);
+}
+
+hipError_t traj_feasibility_params(const noc_family& p, int N, int B, const double* x, const double* u,
+                                   int* ok, const double* tp, hipStream_t s) {
+  return launch_feasibility<TrajParams>(p, N, B, x, u, ok, s, tp);
 }
 
 // total_cost(x, u, bp) = final_cost(x_N) + sum_k stage_cost(x_k, u_k, bp) (PR:53-56, CR:48-51,
 // LD:45-48; the OCP's own callable for a traced family).  One wave64 per trajectory, lanes
 // stride the stages, the wave's butterfly sum; bp per trajectory.
-template <int KIND, int NX, int NU>
+template <int KIND, int NX, int NU, class... TP>
 __global__ __launch_bounds__(64) void total_cost_kernel(noc_family prm, int N, int B,
                                                         const double* x, const double* u,
-                                                        const double* bp, double* cost) {
-#include "deriv_body_total_cost.h"
-}
-
-// per-trajectory cost parameters: as feasibility_params_kernel
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(64) void total_cost_params_kernel(noc_family prm, int N, int B,
-                                                               const double* x, const double* u,
-                                                               const double* bp, double* cost,
-                                                               const double* __restrict__ tp) {
-  {
-    const int bt = blockIdx.x;
-    if (bt >= B) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, bt);
+                                                        const double* bp, double* cost, TP... tp) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  if constexpr (sizeof...(TP) > 0) load_traj_params<NX, NU>(prm, tp..., b);  // wave-uniform b: scalar loads
+  Fam<KIND, NX, NU> f(prm);
+  const double bpb = bp[b];
+  double s = 0.0;
+  for (int k = threadIdx.x; k < N; k += 64) {
+    double xk[NX], uk[NU];
+    NOC_UNROLL for (int i = 0; i < NX; ++i) xk[i] = x[((size_t)b * (N + 1) + k) * NX + i];
+    NOC_UNROLL for (int j = 0; j < NU; ++j) uk[j] = u[((size_t)b * N + k) * NU + j];
+    s += f.stage_cost(xk, uk, bpb);
   }
-#include "deriv_body_total_cost.h"
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t total_cost_params_family(const noc_family& p, int N, int B, const double* x,
-                                           const double* u, const double* bp, double* cost,
-                                           const double* tp, hipStream_t s) {
-  if constexpr (block_params_instance<KIND, NX, NU>()) {
-    hipLaunchKernelGGL((total_cost_params_kernel<KIND, NX, NU>), dim3(B), dim3(64), 0, s, p, N, B, x, u,
-                       bp, cost, tp);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
+  s = wave_sum(s);
+  if (threadIdx.x == 0) {
+    double xN[NX];
+    NOC_UNROLL for (int i = 0; i < NX; ++i) xN[i] = x[((size_t)b * (N + 1) + N) * NX + i];
+    cost[b] = f.final_cost(xN) + s;
   }
 }
 
-hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                             const double* bp, double* cost, const double* tp, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return total_cost_params_family<K, X, U>(p, N, B, x, u, bp, cost, tp, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+template <class... TP>
+static hipError_t launch_total_cost(const noc_family& p, int N, int B, const double* x, const double* u,
+                                    const double* bp, double* cost, hipStream_t s, TP... tp) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (sizeof...(TP) > 0 && !traj_params_instance<K, X, U>()) {
+      return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((total_cost_kernel<K, X, U, TP...>), dim3(B), dim3(64), 0, s, p, N, B, x, u, bp,
+                         cost, tp...);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t total_cost(const noc_family& p, int N, int B, const double* x, const double* u,
                       const double* bp, double* cost, hipStream_t s) {
-#define NOC_FAMILY(K, X, U)                                                                    \
-  if (p.kind == K && p.nx == X && p.nu == U) {                                                 \
-    hipLaunchKernelGGL((total_cost_kernel<K, X, U>), dim3(B), dim3(64), 0, s, p, N, B, x, u, bp, \
-                       cost);                                                                  \
-    return hipGetLastError();                                                                  \
-  }
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return launch_total_cost(p, N, B, x, u, bp, cost, s);
+}
+
+hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x, const double* u,
+                             const double* bp, double* cost, const double* tp, hipStream_t s) {
+  return launch_total_cost<TrajParams>(p, N, B, x, u, bp, cost, s, tp);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -6,9 +6,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/noc_hip.h"
 #include "families_gen.h"
+#include "noc_internal.h"
 #include "small_linalg.h"
 #ifdef NOC_CUSTOM_FAMILY
 // a custom-family build (noc.families.register_family): the generated ODE / discrete map of the
@@ -234,19 +236,46 @@ struct Fam {
   }
 };
 
-// Per-trajectory cost parameters (include/noc_hip.h: NOC_TRAJ_PARAM_DOUBLES): the family q with
-// goal, wx, wu, wf, u_bound of trajectory b's record in place of its own.  The params kernels call
-// this once at entry on their own copy of the family argument and hand the copy to Fam /
-// BlockStruct / CompactSrc, so every consumer (BK_WX constants included) reads the trajectory's
-// values through the same expressions as the shared-parameter instances.  With a wave-uniform b
-// (the persistent solver, the trial kernel) the record is one aligned scalar burst and the fields
-// stay scalar operands.  In the linearise / costate / assemble kernels b is per thread (a block
-// spans several trajectories), so there every thread loads the fields its kernel reads as vector
-// loads (the unread ones are dropped by the compiler) on every launch: up to 29 doubles from a
-// 256-byte record shared by the trajectory's threads, next to the 36+ doubles of blocks per stage.
-// A params kernel guards this load by its own in-range test of b before the shared body runs; the
-// body's text is not touched (its twin must compile to what it did), so that test is restated
-// there: it alone keeps the record read in range, whatever the body's later exits are.
+// Family dispatch: calls fn(K, X, U) -- std::integral_constants, so the callable (a generic
+// lambda) names its kernel instance as kernel<K, X, U> -- for the families.def line that matches
+// p, and returns its result; `none` if no line matches.  A restriction of an instance (the
+// parametrised cost only, nx <= 4, ...) is an `if constexpr` inside the callable, so nothing is
+// instantiated for a family that the restriction leaves out.
+template <class R, class Fn>
+inline R for_family(const noc_family& p, R none, Fn&& fn) {
+#define NOC_FAMILY(K, X, U)                        \
+  if (p.kind == K && p.nx == X && p.nu == U)       \
+    return fn(std::integral_constant<int, K>{}, std::integral_constant<int, X>{}, std::integral_constant<int, U>{});
+#include NOC_FAMILIES_DEF
+#undef NOC_FAMILY
+  return none;
+}
+
+// Per-trajectory cost parameters (include/noc_hip.h: NOC_TRAJ_PARAM_DOUBLES).  A kernel that
+// reads a cost parameter takes the records tp (Bt, NOC_TRAJ_PARAM_DOUBLES) as a trailing argument
+// pack `TP... tp`: empty in the shared-parameter instance, whose argument list is then the plain
+// one, and one TrajParams in the per-trajectory instance (sizeof...(TP) tells them apart at
+// compile time).  (Two kernels keep a `_params_kernel` twin of their own instead,
+// costate_scan_kernel and ipm_solve_kernel: see there.)  Such instances exist for the families
+// with the parametrised cost, not for a registered family's traced costs:
+using TrajParams = const double* __restrict__;
+template <int KIND, int NX, int NU>
+constexpr bool traj_params_instance() { return !Fam<KIND, NX, NU>::kGenCost; }
+
+// load_traj_params: the family q with goal, wx, wu, wf, u_bound of trajectory b's record in place
+// of its own.  A per-trajectory instance calls this once at entry on its own copy of the family
+// argument and hands the copy to Fam / BlockStruct / CompactSrc, so every consumer (BK_WX
+// constants included) reads the trajectory's values through the same expressions as the
+// shared-parameter instance.  With a wave-uniform b (the persistent solvers, the trial,
+// feasibility and total-cost kernels) the record is one aligned scalar burst and the fields stay
+// scalar operands.  In the linearise / costate / assemble / derivatives kernels b is per thread
+// (a block spans several trajectories), so there every thread loads the fields its kernel reads
+// as vector loads (the unread ones are dropped by the compiler) on every launch: up to 29 doubles
+// from a 256-byte record shared by the trajectory's threads, next to the 36+ doubles of blocks
+// per stage.  The call sits in an `if constexpr (sizeof...(TP) > 0)` block at the top of the
+// kernel (of the twin, for the two kernels that keep one), behind an in-range test of b: the kernel's own where that test is the kernel's first
+// exit on the same index, else a test of its own in that block -- it alone keeps the record read
+// in range, whatever the kernel's later exits are.
 template <int NX, int NU>
 NOC_DEV void load_traj_params(noc_family& q, const double* __restrict__ tp, int b) {
   const double* __restrict__ r = tp + (size_t)b * NOC_TRAJ_PARAM_DOUBLES;

@@ -81,23 +81,51 @@ __global__ __launch_bounds__(256) void promote_kernel(noc_ipm_ws w) {
 // COMPACT (here and in the costate / assemble kernels): w.A, w.B, w.Q, w.R, w.M are the compact
 // tiled fields (block_struct.h: the variable entries only, the layout noc_ipm_solve keeps there);
 // the constants are rebuilt where a block is read -- the same doubles the dense fields hold
-template <int KIND, int NX, int NU, bool COMPACT>
-__global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_ws w) {
-#include "ipm_body_linearize.h"
-}
-// per-trajectory cost parameters (noc_ipm_prepare_params): the same body, dense blocks, on a
-// family argument that first takes trajectory b's goal, wx, wu, wf, u_bound from its record in tp
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void linearize_params_kernel(noc_family prm, noc_ipm_ws w,
-                                                              const double* __restrict__ tp) {
-  constexpr bool COMPACT = false;
-  {
+// Per-trajectory cost parameters (noc_ipm_prepare_params, noc_ipm_trial_params): TP... tp is
+// empty, or the records (ipm_family.h: TrajParams) -- then the family argument first takes
+// trajectory b's goal, wx, wu, wf, u_bound from its record.  Those instances run on dense blocks.
+template <int KIND, int NX, int NU, bool COMPACT, class... TP>
+__global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_ws w, TP... tp) {
+  if constexpr (sizeof...(TP) > 0) {  // b = t / (chunk slots x lanes) per thread: vector loads
     const long long tt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long per = (long long)((w.N + w.lanes - 1) / w.lanes) * w.lanes;
-    if (tt >= (long long)w.Bt * per) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, (int)(tt / per));
+    if (tt >= (long long)w.Bt * per) return;  // keeps the record read in range
+    load_traj_params<NX, NU>(prm, tp..., (int)(tt / per));
   }
-#include "ipm_body_linearize.h"
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = w.N, L = w.lanes;
+  const Chunks ch(N, L);
+  if (t >= (long long)w.Bt * ch.cmax * L) return;
+  const int b = (int)(t / ((long long)ch.cmax * L));
+  const int rem = (int)(t % ((long long)ch.cmax * L));
+  const int j = rem / L, l = rem % L;
+  if (j >= ch.len(l) || w.phase[b] != NOC_PHASE_LINEARIZE) return;
+  const int k = ch.start(l) + j;
+  const size_t tn = (size_t)b * N + k;
+  Fam<KIND, NX, NU> f(prm);
+  const double bp = w.bp[b];
+  double x[NX], u[NU];
+  gload<NX>(w.x + ((size_t)b * (N + 1) + k) * NX, x);
+  NOC_UNROLL for (int i = 0; i < NU; ++i) u[i] = w.u[tn * NU + i];
+  double fx[NX * NX], fu[NX * NU], cx[NX], cu[NU];  // all stored tiled
+  f.jac(x, u, fx, fu);
+  f.stage_grad(x, u, bp, cx, cu);
+  if constexpr (COMPACT) {
+    using BS = BlockStruct<KIND, NX, NU, true>;
+    constexpr int VA = BS::template nv<BF_A>(), VB = BS::template nv<BF_B>();
+    double va[VA > 0 ? VA : 1], vb[VB > 0 ? VB : 1];
+    BS::template compress<BF_A>(fx, va);
+    BS::template compress<BF_B>(fu, vb);
+    if constexpr (VA > 0) tstore_rt<VA>(w.A, L, ch.cmax, b, j, l, va);
+    if constexpr (VB > 0) tstore_rt<VB>(w.B, L, ch.cmax, b, j, l, vb);
+  } else {
+    tstore_rt<NX * NX>(w.A, L, ch.cmax, b, j, l, fx);
+    tstore_rt<NX * NU>(w.B, L, ch.cmax, b, j, l, fu);
+  }
+  tstore_rt<NX>(w.cx, L, ch.cmax, b, j, l, cx);
+  tstore_rt<NU>(w.cu, L, ch.cmax, b, j, l, cu);
+  const double lc = f.stage_cost(x, u, bp);
+  tstore_rt<1>(w.lc, L, ch.cmax, b, j, l, &lc);
 }
 
 // Costates as a reverse affine scan over the horizon (the par_costates pattern, C:34-40),
@@ -106,67 +134,99 @@ __global__ __launch_bounds__(256) void linearize_params_kernel(noc_family prm, n
 // plus, per trajectory: ru_k = cu_k + B_k' lambda_{k+1} (P:34, tiled), total cost (P:142),
 // max|ru| (P:158), ||cu||_F (P:116), the regularisation fed to the KKT solve and the terminal
 // Hessian hessian(final_cost) (S:66).
+// (This kernel keeps a twin for the per-trajectory records, and the two share their body through
+// ipm_body_costate.h, included between their braces: folded into one kernel like the others, by a
+// trailing argument pack or by a force-inlined body function, the (8, 4) instances' register
+// allocation moved -- profiles/r10/params_fold/README.md.)
 template <int KIND, int NX, int NU, int L, bool COMPACT>
 __global__ __launch_bounds__(64) void costate_scan_kernel(noc_family prm, noc_ipm_ws w, int mode) {
 #include "ipm_body_costate.h"
 }
-// per-trajectory cost parameters: as linearize_params_kernel
+// per-trajectory cost parameters: b per L-lane segment, vector loads; dense blocks
 template <int KIND, int NX, int NU, int L>
 __global__ __launch_bounds__(64) void costate_scan_params_kernel(noc_family prm, noc_ipm_ws w, int mode,
                                                                 const double* __restrict__ tp) {
   constexpr bool COMPACT = false;
   {
     const int bt = (int)((blockIdx.x * blockDim.x + threadIdx.x) / L);
-    if (bt >= w.Bt) return;  // as the body
+    if (bt >= w.Bt) return;  // as the body: keeps the record read in range
     load_traj_params<NX, NU>(prm, tp, bt);
   }
 #include "ipm_body_costate.h"
 }
 
+template <int KIND, int NX, int NU, int L, bool COMPACT, class... TP>
+static void launch_costate_l(const noc_family& p, const noc_ipm_ws& w, int mode, unsigned grid, hipStream_t s,
+                             TP... tp) {
+  if constexpr (sizeof...(TP) > 0)
+    hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, L>), dim3(grid), dim3(64), 0, s, p, w, mode, tp...);
+  else
+    hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, L, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode);
+}
 
-template <int KIND, int NX, int NU>
-static void launch_costate_params(const noc_family& p, const noc_ipm_ws& w, int mode, const double* tp,
-                                  hipStream_t s) {
+template <int KIND, int NX, int NU, bool COMPACT, class... TP>
+static void launch_costate(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s, TP... tp) {
   const int L = w.lanes;
   const unsigned grid = (unsigned)(((long long)w.Bt * L + 63) / 64);
   switch (L) {
-    case 64: hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, 64>), dim3(grid), dim3(64), 0, s, p, w, mode, tp); break;
-    case 32: hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, 32>), dim3(grid), dim3(64), 0, s, p, w, mode, tp); break;
-    case 16: hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, 16>), dim3(grid), dim3(64), 0, s, p, w, mode, tp); break;
-    case 8: hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, 8>), dim3(grid), dim3(64), 0, s, p, w, mode, tp); break;
-    default: hipLaunchKernelGGL((costate_scan_params_kernel<KIND, NX, NU, 1>), dim3(grid), dim3(64), 0, s, p, w, mode, tp); break;
+    case 64: launch_costate_l<KIND, NX, NU, 64, COMPACT, TP...>(p, w, mode, grid, s, tp...); break;
+    case 32: launch_costate_l<KIND, NX, NU, 32, COMPACT, TP...>(p, w, mode, grid, s, tp...); break;
+    case 16: launch_costate_l<KIND, NX, NU, 16, COMPACT, TP...>(p, w, mode, grid, s, tp...); break;
+    case 8: launch_costate_l<KIND, NX, NU, 8, COMPACT, TP...>(p, w, mode, grid, s, tp...); break;
+    default: launch_costate_l<KIND, NX, NU, 1, COMPACT, TP...>(p, w, mode, grid, s, tp...); break;
   }
 }
 
-template <int KIND, int NX, int NU, bool COMPACT>
-static void launch_costate(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
-  const int L = w.lanes;
-  const unsigned grid = (unsigned)(((long long)w.Bt * L + 63) / 64);
-  switch (L) {
-    case 64: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 64, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 32: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 32, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 16: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 16, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    case 8: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 8, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-    default: hipLaunchKernelGGL((costate_scan_kernel<KIND, NX, NU, 1, COMPACT>), dim3(grid), dim3(64), 0, s, p, w, mode); break;
-  }
-}
-
-template <int KIND, int NX, int NU, bool COMPACT>
-__global__ __launch_bounds__(256) void assemble_kernel(noc_family prm, noc_ipm_ws w, int terminal) {
-#include "ipm_body_assemble.h"
-}
-// per-trajectory cost parameters: as linearize_params_kernel
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void assemble_params_kernel(noc_family prm, noc_ipm_ws w, int terminal,
-                                                             const double* __restrict__ tp) {
-  constexpr bool COMPACT = false;
-  {
+template <int KIND, int NX, int NU, bool COMPACT, class... TP>
+__global__ __launch_bounds__(256) void assemble_kernel(noc_family prm, noc_ipm_ws w, int terminal, TP... tp) {
+  if constexpr (sizeof...(TP) > 0) {  // b = t / (chunk slots x lanes) per thread: vector loads
     const long long tt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long per = (long long)((w.N + w.lanes - 1) / w.lanes) * w.lanes;
-    if (tt >= (long long)w.Bt * per) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, (int)(tt / per));
+    if (tt >= (long long)w.Bt * per) return;  // keeps the record read in range
+    load_traj_params<NX, NU>(prm, tp..., (int)(tt / per));
   }
-#include "ipm_body_assemble.h"
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = w.N, L = w.lanes;
+  const Chunks ch(N, L);
+  if (t >= (long long)w.Bt * ch.cmax * L) return;
+  const int b = (int)(t / ((long long)ch.cmax * L));
+  const int rem = (int)(t % ((long long)ch.cmax * L));
+  const int j = rem / L, l = rem % L;
+  if (j >= ch.len(l) || w.phase[b] != NOC_PHASE_LINEARIZE) return;
+  const int k = ch.start(l) + j;
+  const size_t tn = (size_t)b * N + k;
+  Fam<KIND, NX, NU> f(prm);
+  const double bp = w.bp[b];
+  double x[NX], u[NU], lam[NX];
+  gload<NX>(w.x + ((size_t)b * (N + 1) + k) * NX, x);
+  NOC_UNROLL for (int i = 0; i < NU; ++i) u[i] = w.u[tn * NU + i];
+  gload<NX>(w.lam + ((size_t)b * (N + 1) + k + 1) * NX, lam);
+  // Q = cxx + l.fxx ; R = cuu + l.fuu ; M = cxu + l.fxu  (P:35-37), l = lambda_{k+1}
+  double Q[NX * NX], R[NU * NU], M[NX * NU];
+  f.stage_hess(x, u, bp, Q, R, M);
+  f.add_hess_l(x, u, lam, Q, R, M);
+  Sym<NX> Qs;
+  Sym<NU> Rs;
+  NOC_UNROLL for (int i = 0; i < NX; ++i)
+    NOC_UNROLL for (int jj = i; jj < NX; ++jj) Qs(i, jj) = (i == jj) ? Q[i * NX + i] : 0.5 * (Q[i * NX + jj] + Q[jj * NX + i]);
+  NOC_UNROLL for (int i = 0; i < NU; ++i)
+    NOC_UNROLL for (int jj = i; jj < NU; ++jj) Rs(i, jj) = (i == jj) ? R[i * NU + i] : 0.5 * (R[i * NU + jj] + R[jj * NU + i]);
+  if constexpr (COMPACT) {
+    using BS = BlockStruct<KIND, NX, NU, true>;
+    constexpr int VQ = BS::template nv<BF_Q>(), VR = BS::template nv<BF_R>(), VM = BS::template nv<BF_M>();
+    double vq[VQ > 0 ? VQ : 1], vr[VR > 0 ? VR : 1], vm[VM > 0 ? VM : 1];
+    BS::template compress<BF_Q>(Qs.v, vq);
+    BS::template compress<BF_R>(Rs.v, vr);
+    BS::template compress<BF_M>(M, vm);
+    if constexpr (VQ > 0) tstore_rt<VQ>(w.Q, L, ch.cmax, b, j, l, vq);
+    if constexpr (VR > 0) tstore_rt<VR>(w.R, L, ch.cmax, b, j, l, vr);
+    if constexpr (VM > 0) tstore_rt<VM>(w.M, L, ch.cmax, b, j, l, vm);
+  } else {
+    tstore_rt<Sym<NX>::SZ>(w.Q, L, ch.cmax, b, j, l, Qs.v);
+    tstore_rt<Sym<NU>::SZ>(w.R, L, ch.cmax, b, j, l, Rs.v);
+    tstore_rt<NX * NU>(w.M, L, ch.cmax, b, j, l, M);
+  }
+  if (terminal == NOC_TERMINAL_STAGE0 && k == 0) gstore<NX * NX>(w.P + (size_t)b * NX * NX, Q);  // P:73
 }
 
 __global__ __launch_bounds__(256) void mark_solve_kernel(noc_ipm_ws w) {
@@ -180,21 +240,74 @@ __global__ __launch_bounds__(256) void mark_solve_kernel(noc_ipm_ws w) {
 // ------------------------------------------------------------------------------------------------
 // trial point + Newton / barrier logic: one wave64 per trajectory (4 per 256-thread block)
 
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void trial_kernel(noc_family prm, noc_ipm_ws w, int mode) {
-#include "ipm_body_trial.h"
-}
-// per-trajectory cost parameters (noc_ipm_trial_params): as linearize_params_kernel; the
-// trajectory is wave-uniform here
-template <int KIND, int NX, int NU>
-__global__ __launch_bounds__(256) void trial_params_kernel(noc_family prm, noc_ipm_ws w, int mode,
-                                                          const double* __restrict__ tp) {
-  {
+template <int KIND, int NX, int NU, class... TP>
+__global__ __launch_bounds__(256) void trial_kernel(noc_family prm, noc_ipm_ws w, int mode, TP... tp) {
+  if constexpr (sizeof...(TP) > 0) {  // the trajectory is wave-uniform here: scalar loads
     const int bt = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (bt >= w.Bt) return;  // as the body
-    load_traj_params<NX, NU>(prm, tp, __builtin_amdgcn_readfirstlane(bt));
+    if (bt >= w.Bt) return;  // keeps the record read in range
+    load_traj_params<NX, NU>(prm, tp..., __builtin_amdgcn_readfirstlane(bt));
   }
-#include "ipm_body_trial.h"
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= w.Bt || w.phase[b] != NOC_PHASE_SOLVE) return;  // uniform per wave
+  Fam<KIND, NX, NU> f(prm);
+  const int N = w.N;
+  const double bp = w.bp[b];
+  const double* X = w.x + (size_t)b * (N + 1) * NX;
+  const double* DX = w.dx + (size_t)b * (N + 1) * NX;
+  const double* U = w.u + (size_t)b * N * NU;
+  const double* DU = w.du + (size_t)b * N * NU;
+  // lane l sums the stages of horizon chunk l (the 64-lane chunk geometry) and the last lane adds
+  // the final cost: the same summation order as the persistent solver (ipm_persistent.hip), so
+  // both drivers take identical accept / reject decisions
+  double csum = 0.0;
+  int ok = 1;
+  const Chunks ch(N, 64);
+  for (int k = ch.start(lane); k < ch.start(lane) + ch.len(lane); ++k) {
+    double xt[NX], ut[NU];
+    NOC_UNROLL for (int i = 0; i < NX; ++i) xt[i] = X[(size_t)k * NX + i] + DX[(size_t)k * NX + i];
+    NOC_UNROLL for (int j = 0; j < NU; ++j) ut[j] = U[(size_t)k * NU + j] + DU[(size_t)k * NU + j];
+    ok &= f.feasible(xt, ut) ? 1 : 0;
+    csum += f.stage_cost(xt, ut, bp);
+  }
+  if (lane == 63) {
+    double xt[NX];
+    NOC_UNROLL for (int i = 0; i < NX; ++i) xt[i] = X[(size_t)N * NX + i] + DX[(size_t)N * NX + i];
+    csum += f.final_cost(xt);
+  }
+  csum = wave_sum(csum);
+  const bool traj_ok = __all(ok);
+  // new_cost = where(feasible, total_cost(trial), inf)   (P:159-163, S:126-129)
+  const double new_cost = traj_ok ? csum : INFINITY;
+  // the accept rule and barrier schedule of every solver (ipm_schedule.h); no solve cap here, so
+  // the retry accounting has the whole retry loop for room
+  IpmState s;
+  s.load(w, b);
+  const AcceptOutcome o = accept_step(s, mode, new_cost, w.pred[b], w.feasible[b] != 0, w.flags, 501);
+  if (o.take) {  // x <- x + dx, u <- u + du
+    double* Xw = w.x + (size_t)b * (N + 1) * NX;
+    double* Uw = w.u + (size_t)b * N * NU;
+    for (int k = lane; k <= N; k += 64) {
+      NOC_UNROLL for (int i = 0; i < NX; ++i) Xw[(size_t)k * NX + i] += DX[(size_t)k * NX + i];
+      if (k < N) NOC_UNROLL for (int j = 0; j < NU; ++j) Uw[(size_t)k * NU + j] += DU[(size_t)k * NU + j];
+    }
+  }
+  if (lane != 0) return;
+  if (w.repeats) w.repeats[b] += o.rep;
+  w.kkt_solves[b] = s.solves;
+  w.inner[b] = s.inner;
+  w.it[b] = s.it;
+  w.rp[b] = s.rp;
+  w.rinc[b] = s.rinc;
+  if (o.stage_done) {
+    w.total_it[b] = s.total_it;
+    w.bp[b] = s.bp;
+  }
+  // the rollout of a new stage happens in the next step (ROLLOUT_PENDING, see rollout_kernel)
+  int phase = resume_point(o.stage_done, o.relinearize, s.bp, w.flags);
+  if (phase == NOC_PHASE_ROLLOUT) phase = NOC_PHASE_ROLLOUT_PENDING;
+  if (phase == NOC_PHASE_SOLVE) w.reg[b] = candidate_reg(mode, s.rp, s.gnorm);
+  w.phase[b] = phase;
 }
 
 __global__ __launch_bounds__(256) void init_kernel(noc_ipm_ws w, double bp0) {
@@ -223,15 +336,15 @@ static hipError_t rollout_t(const noc_family& p, const noc_ipm_ws& w, hipStream_
 }
 
 // linearise + costates + LQ blocks for phase-LINEARIZE trajectories, then LINEARIZE -> SOLVE
-template <int KIND, int NX, int NU, bool COMPACT>
+template <int KIND, int NX, int NU, bool COMPACT, class... TP>
 static hipError_t prepare_main_c(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                                 hipStream_t s) {
+                                 hipStream_t s, TP... tp) {
   const int bt_grid = (w.Bt + 255) / 256;
   const long long cmax = (w.N + w.lanes - 1) / w.lanes;
   const unsigned st_grid = (unsigned)(((long long)w.Bt * cmax * w.lanes + 255) / 256);
-  hipLaunchKernelGGL((linearize_kernel<KIND, NX, NU, COMPACT>), dim3(st_grid), dim3(256), 0, s, p, w);
-  launch_costate<KIND, NX, NU, COMPACT>(p, w, mode, s);
-  hipLaunchKernelGGL((assemble_kernel<KIND, NX, NU, COMPACT>), dim3(st_grid), dim3(256), 0, s, p, w, terminal);
+  hipLaunchKernelGGL((linearize_kernel<KIND, NX, NU, COMPACT, TP...>), dim3(st_grid), dim3(256), 0, s, p, w, tp...);
+  launch_costate<KIND, NX, NU, COMPACT, TP...>(p, w, mode, s, tp...);  // TP named: deduction would drop its restrict
+  hipLaunchKernelGGL((assemble_kernel<KIND, NX, NU, COMPACT, TP...>), dim3(st_grid), dim3(256), 0, s, p, w, terminal, tp...);
   hipLaunchKernelGGL(mark_solve_kernel, dim3(bt_grid), dim3(256), 0, s, w);
   return hipGetLastError();
 }
@@ -244,124 +357,70 @@ static hipError_t prepare_main_t(const noc_family& p, const noc_ipm_ws& w, int m
                  : prepare_main_c<KIND, NX, NU, false>(p, w, mode, terminal, s);
 }
 
-template <int KIND, int NX, int NU>
-static hipError_t prepare_t(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                            bool compact, hipStream_t s) {
-  hipError_t e = rollout_t<KIND, NX, NU>(p, w, s, 1);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
-  return prepare_main_t<KIND, NX, NU>(p, w, mode, terminal, compact, s);
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t trial_t(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
-  const unsigned grid = (unsigned)((w.Bt + 3) / 4);
-  hipLaunchKernelGGL((trial_kernel<KIND, NX, NU>), dim3(grid), dim3(256), 0, s, p, w, mode);
-  return hipGetLastError();
-}
-
-// family dispatch: one instantiation per NOC_FAMILY line of families.def
-hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                       bool compact, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return prepare_t<K, X, U>(p, w, mode, terminal, compact, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-hipError_t ipm_rollout(const noc_family& p, const noc_ipm_ws& w, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return rollout_t<K, X, U>(p, w, s, 0);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                            bool compact, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
 hipError_t ipm_promote(const noc_ipm_ws& w, hipStream_t s) {
   hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
   return hipGetLastError();
 }
 
-hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return trial_t<K, X, U>(p, w, mode, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-// ---- per-trajectory cost parameters: the params forms of prepare and trial (the rollout needs
-// none: it reads dt and the dynamics only).  Dense blocks.
-template <int KIND, int NX, int NU>
-constexpr bool traj_params_instance() { return !Fam<KIND, NX, NU>::kGenCost; }
-
-template <int KIND, int NX, int NU>
-static hipError_t prepare_params_t(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                                   int terminal, hipStream_t s) {
-  if constexpr (traj_params_instance<KIND, NX, NU>()) {
-    hipError_t e = rollout_t<KIND, NX, NU>(p, w, s, 1);
+// family dispatch (ipm_family.h: for_family): one instantiation per NOC_FAMILY line of families.def
+hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
+                       bool compact, hipStream_t s) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    hipError_t e = rollout_t<K, X, U>(p, w, s, 1);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
-    const int bt_grid = (w.Bt + 255) / 256;
-    const long long cmax = (w.N + w.lanes - 1) / w.lanes;
-    const unsigned st_grid = (unsigned)(((long long)w.Bt * cmax * w.lanes + 255) / 256);
-    hipLaunchKernelGGL((linearize_params_kernel<KIND, NX, NU>), dim3(st_grid), dim3(256), 0, s, p, w, tp);
-    launch_costate_params<KIND, NX, NU>(p, w, mode, tp, s);
-    hipLaunchKernelGGL((assemble_params_kernel<KIND, NX, NU>), dim3(st_grid), dim3(256), 0, s, p, w, terminal, tp);
-    hipLaunchKernelGGL(mark_solve_kernel, dim3(bt_grid), dim3(256), 0, s, w);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
+    return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
+  });
 }
 
-template <int KIND, int NX, int NU>
-static hipError_t trial_params_t(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                                 hipStream_t s) {
-  if constexpr (traj_params_instance<KIND, NX, NU>()) {
-    hipLaunchKernelGGL((trial_params_kernel<KIND, NX, NU>), dim3((unsigned)((w.Bt + 3) / 4)), dim3(256), 0, s, p,
-                       w, mode, tp);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
+hipError_t ipm_rollout(const noc_family& p, const noc_ipm_ws& w, hipStream_t s) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) { return rollout_t<K, X, U>(p, w, s, 0); });
 }
 
+hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
+                            bool compact, hipStream_t s) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
+  });
+}
+
+// per-trajectory cost parameters: the params form of prepare (the rollout needs none: it reads dt
+// and the dynamics only).  Dense blocks.
 hipError_t ipm_prepare_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
                               int terminal, hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return prepare_params_t<K, X, U>(p, w, tp, mode, terminal, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (traj_params_instance<K, X, U>()) {
+      hipError_t e = rollout_t<K, X, U>(p, w, s, 1);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
+      return prepare_main_c<K, X, U, false, TrajParams>(p, w, mode, terminal, s, tp);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+// tp: nothing, or the records (a TrajParams)
+template <class... TP>
+static hipError_t launch_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s, TP... tp) {
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (sizeof...(TP) > 0 && !traj_params_instance<K, X, U>()) {
+      return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((trial_kernel<K, X, U, TP...>), dim3((unsigned)((w.Bt + 3) / 4)), dim3(256), 0, s, p, w,
+                         mode, tp...);
+      return hipGetLastError();
+    }
+  });
+}
+
+hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
+  return launch_trial(p, w, mode, s);
 }
 
 hipError_t ipm_trial_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
                             hipStream_t s) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return trial_params_t<K, X, U>(p, w, tp, mode, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
-}
-
-// a family with the parametrised quadratic cost (not a registered family's traced costs)
-bool traj_params_supported(const noc_family& p) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return traj_params_instance<K, X, U>();
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return false;
+  return launch_trial<TrajParams>(p, w, mode, s, tp);
 }
 
 hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s) {
@@ -369,12 +428,14 @@ hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the library has instances for p (a families.def line) ...
 bool family_supported(const noc_family& p) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return true;
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return false;
+  return for_family(p, false, [](auto, auto, auto) { return true; });
+}
+
+// ... with the parametrised quadratic cost (not a registered family's traced costs)
+bool traj_params_supported(const noc_family& p) {
+  return for_family(p, false, [](auto K, auto X, auto U) { return traj_params_instance<K, X, U>(); });
 }
 
 }  // namespace noc

@@ -107,6 +107,17 @@ __host__ __device__ constexpr int xlds_off(int N, int spec = 1, int wv = 0) {
 // SPEC: waves per trajectory, each solving one candidate of the regularisation's failure chain
 // (speculative retries, below); 1 = the plain solver.  SPEC > 1 needs XLDS (every wave keeps its
 // own copy of x, u).
+// This kernel keeps a twin for the per-trajectory records, ipm_solve_params_kernel, and the two
+// share their body through ipm_solve_body.h, included between their braces: folded into one
+// kernel like the building blocks, by a trailing argument pack or by a force-inlined body
+// function, cart-pole instances' scratch moved (profiles/r10/params_fold/README.md).  The twin
+// (noc_ipm_solve_params) is the one-wave solver on structure-aware blocks (STRUCT, SPEC = 1): the
+// family argument first takes goal, wx, wu, wf, u_bound of the workgroup's trajectory from its record in
+// tp (Bt, NOC_TRAJ_PARAM_DOUBLES).  The record follows the trajectory, not the workgroup (w.order
+// permutes workgroups); the index is wave-uniform (said to the compiler by readfirstlane) and the
+// loads come before any store, so the record arrives as one scalar burst and the fields stay
+// scalar operands like kernel arguments.  Every consumer -- Fam, the BK_WX constants of
+// fold_consts / expand and of the inlined KKT scan's CompactSrc -- reads `prm`, so none is missed.
 template <int KIND, int NX, int NU, int WPS, bool RESUME, bool XLDS, bool STRUCT, int SPEC = 1>
 __global__ __launch_bounds__(64 * SPEC, WPS) void ipm_solve_kernel(noc_family prm, noc_ipm_ws w, int mode,
                                                                 int terminal, double bp0,
@@ -114,14 +125,6 @@ __global__ __launch_bounds__(64 * SPEC, WPS) void ipm_solve_kernel(noc_family pr
 #include "ipm_solve_body.h"
 }
 
-// The one-wave solver with per-trajectory cost parameters (noc_ipm_solve_params): the same body
-// (structure-aware blocks, one candidate) on a family argument that first takes goal, wx, wu, wf,
-// u_bound of the workgroup's trajectory from its record in tp (Bt, NOC_TRAJ_PARAM_DOUBLES).  The
-// record follows the trajectory, not the workgroup (w.order permutes workgroups); the index is
-// wave-uniform (said to the compiler by readfirstlane) and the loads come before any store, so the
-// record arrives as one scalar burst and the fields stay scalar operands like kernel arguments.
-// Every consumer -- Fam, the BK_WX constants of fold_consts / expand and of the inlined KKT scan's
-// CompactSrc -- reads `prm`, so none is missed.
 template <int KIND, int NX, int NU, int WPS, bool RESUME, bool XLDS>
 __global__ __launch_bounds__(64, WPS) void ipm_solve_params_kernel(noc_family prm, noc_ipm_ws w,
                                                                    const double* __restrict__ tp, int mode,
@@ -395,20 +398,9 @@ template <int NX>
 constexpr bool persistent_instance() { return NX <= 4; }
 
 bool ipm_solve_supported(const noc_family& p, int N, int lanes) {
-  if (lanes != PL || !family_supported(p)) return false;
-  bool inst = false;
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) inst = persistent_instance<X>();
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return inst && solve_lds_bytes(p.nx, p.nu, N) > 0;
-}
-
-template <int K, int X, int U>
-static hipError_t solve_family(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                               double bp0, int max_solves, hipStream_t s) {
-  if constexpr (persistent_instance<X>()) return solve_t<K, X, U>(p, w, mode, terminal, bp0, max_solves, s);
-  else return hipErrorInvalidValue;
+  if (lanes != PL) return false;
+  return for_family(p, false, [](auto, auto X, auto) { return persistent_instance<X>(); }) &&
+         solve_lds_bytes(p.nx, p.nu, N) > 0;
 }
 
 // The wide kernel (ipm_wide.hip: 4 waves and the LDS of one CU per trajectory) when the batch
@@ -443,44 +435,33 @@ hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int ter
     return ipm_solve_wide(p, w, mode, terminal, bp0, max_solves, nullptr, nullptr, w.Bt,
                           wide_waves(p, w, cus), s);
   }
-#define NOC_FAMILY(K, X, U)                                                              \
-  if (p.kind == K && p.nx == X && p.nu == U)                                             \
-    return solve_family<K, X, U>(p, w, mode, terminal, bp0, max_solves, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (persistent_instance<X>()) return solve_t<K, X, U>(p, w, mode, terminal, bp0, max_solves, s);
+    else return hipErrorInvalidValue;
+  });
 }
 
 // Per-trajectory cost parameters (noc_ipm_solve_params): always the one-wave kernel, with the
 // register budget (one or two waves per SIMD) and the x, u placement solve_t / solve_w choose for
 // the same batch -- never the wide kernel, speculative candidates or the heavy-first split, whose
 // instances read the shared family argument.
-template <int K, int X, int U>
-static hipError_t solve_params_family(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                                      int terminal, double bp0, int max_solves, hipStream_t s) {
-  if constexpr (persistent_instance<X>() && !Fam<K, X, U>::kGenCost) {
-    const size_t lds = solve_lds_bytes(X, U, w.N);
-    if (lds == 0) return hipErrorInvalidValue;
-    if constexpr (one_wave_instance<K>()) {
-      static const int simds = device_simds();
-      static const char* env = getenv("NOC_PERSIST_WAVES");
-      if (env ? atoi(env) == 1 : (simds > 0 && w.Bt <= simds))
-        return solve_w<K, X, U, 1>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
-    }
-    return solve_w<K, X, U, 2>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
 hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
                             int terminal, double bp0, int max_solves, hipStream_t s) {
-#define NOC_FAMILY(K, X, U)                                                              \
-  if (p.kind == K && p.nx == X && p.nu == U)                                             \
-    return solve_params_family<K, X, U>(p, w, tp, mode, terminal, bp0, max_solves, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (persistent_instance<X>() && traj_params_instance<K, X, U>()) {
+      const size_t lds = solve_lds_bytes(X, U, w.N);
+      if (lds == 0) return hipErrorInvalidValue;
+      if constexpr (one_wave_instance<K>()) {
+        static const int simds = device_simds();
+        static const char* env = getenv("NOC_PERSIST_WAVES");
+        if (env ? atoi(env) == 1 : (simds > 0 && w.Bt <= simds))
+          return solve_w<K, X, U, 1>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
+      }
+      return solve_w<K, X, U, 2>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 }  // namespace noc

@@ -720,11 +720,7 @@ static size_t wide_lds_t(int N, int W) {
   return bytes <= 160 * 1024 - 1024 ? bytes : 0;
 }
 size_t wide_lds_bytes(const noc_family& p, int N, int W) {
-#define NOC_FAMILY(K, X, U) \
-  if (p.kind == K && p.nx == X && p.nu == U) return wide_lds_t<K, X, U>(N, W);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return 0;
+  return for_family(p, (size_t)0, [&](auto K, auto X, auto U) { return wide_lds_t<K, X, U>(N, W); });
 }
 
 // Waves per trajectory: 4 when the batch leaves CUs idle (B <= #CUs: one workgroup per CU), 2
@@ -738,25 +734,6 @@ int wide_waves(const noc_family& p, const noc_ipm_ws& w, int cus) {
   return (two > 0 && two <= 80 * 1024 - 512) ? 2 : 4;
 }
 
-template <int K, int X, int U>
-static hipError_t wide_family(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                              double bp0, int max_solves, const int* idx, const int* count,
-                              int grid, int W, hipStream_t s) {
-  if constexpr (X <= 4) {
-    const size_t lds = wide_lds_t<K, X, U>(w.N, W);
-    if (lds == 0 || grid <= 0) return hipErrorInvalidValue;
-    if (W == 2)
-      hipLaunchKernelGGL((ipm_wide_kernel<K, X, U, 2>), dim3(grid), dim3(128), lds, s, p, w, mode,
-                         terminal, bp0, max_solves, idx, count);
-    else
-      hipLaunchKernelGGL((ipm_wide_kernel<K, X, U, kWideWaves>), dim3(grid), dim3(64 * kWideWaves),
-                         lds, s, p, w, mode, terminal, bp0, max_solves, idx, count);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
 bool ipm_wide_supported(const noc_family& p, int N) {
   return family_supported(p) && p.nx <= 4 && wide_lds_bytes(p, N, kWideWaves) > 0;
 }
@@ -764,12 +741,21 @@ bool ipm_wide_supported(const noc_family& p, int N) {
 hipError_t ipm_solve_wide(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
                           double bp0, int max_solves, const int* idx, const int* count, int grid,
                           int W, hipStream_t s) {
-#define NOC_FAMILY(K, X, U)                                                              \
-  if (p.kind == K && p.nx == X && p.nu == U)                                             \
-    return wide_family<K, X, U>(p, w, mode, terminal, bp0, max_solves, idx, count, grid, W, s);
-#include NOC_FAMILIES_DEF
-#undef NOC_FAMILY
-  return hipErrorInvalidValue;
+  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (X <= 4) {
+      const size_t lds = wide_lds_t<K, X, U>(w.N, W);
+      if (lds == 0 || grid <= 0) return hipErrorInvalidValue;
+      if (W == 2)
+        hipLaunchKernelGGL((ipm_wide_kernel<K, X, U, 2>), dim3(grid), dim3(128), lds, s, p, w, mode,
+                           terminal, bp0, max_solves, idx, count);
+      else
+        hipLaunchKernelGGL((ipm_wide_kernel<K, X, U, kWideWaves>), dim3(grid), dim3(64 * kWideWaves),
+                           lds, s, p, w, mode, terminal, bp0, max_solves, idx, count);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 }  // namespace noc

@@ -1,5 +1,5 @@
 """The first backward passes of interior-point DDP at one barrier value (D:98-186), restated in high
-precision, and the seeded cases on which the one-launch kernel (csrc/ddp_solve_body.h) is held to
+precision, and the seeded cases on which the one-launch kernel (ddp_solve_kernel, csrc/ddp_persistent.hip) is held to
 them.  A helper, not a test: CPU only, nothing here imports torch or touches a device.
 
 Reference.  reference_passes(name, x0, u0, bp, K) follows oracle.noc_oracle.ddp statement for

@@ -341,7 +341,7 @@ def test_final_cost_grad_second_block():
         g1, H1 = final_cost_grad(ocp, xN[b:b + 1], hessian=True)
         assert torch.equal(g[b], g1[0]) and torch.equal(H[b], H1[0]), b
     assert not torch.equal(g[255], g[256])
-    # final_derivs_params_kernel: the same boundary with one record per trajectory
+    # final_derivs_kernel with records: the same boundary with one record per trajectory
     from test_ddp_params_gpu import _rows
     params, solo = _rows(ocp.family, B)
     gp, Hp = final_cost_grad(ocp, xN, hessian=True, params=params)

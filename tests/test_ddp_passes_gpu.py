@@ -1,4 +1,4 @@
-"""GPU: the first passes of the one-launch DDP kernel (csrc/ddp_solve_body.h behind noc_ddp_solve_ex
+"""GPU: the first passes of the one-launch DDP kernel (ddp_solve_kernel, csrc/ddp_persistent.hip, behind noc_ddp_solve_ex
 and noc_ddp_solve_params) against the high-precision reference of tests/ddp_pass_cases.py.
 
 The kernel carries its own copy of the stage derivatives, the dynamics-Hessian record, the

@@ -310,6 +310,52 @@ def test_uniform_parameters_equal_the_shared_path(monkeypatch):
     _assert_equal(shared, with_params)
 
 
+def _bits(t):
+    return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+
+@pytest.mark.parametrize("name,lanes,N,Bt", [("pendulum", 8, 7, 5), ("pendulum", 64, 7, 5),
+                                             ("cartpole", 8, 7, 5), ("cartpole", 64, 7, 5),
+                                             ("linear8", 1, 3, 9)])
+def test_uniform_parameters_equal_the_shared_path_launch_per_phase(name, lanes, N, Bt):
+    """The launch-per-phase kernels with uniform records against the shared-parameter instances,
+    every workspace array and counter bit for bit after each of a few steps, where one 256-thread
+    block of linearise / assemble spans several trajectories, so the record index is formed per
+    thread: N = 7 (chunks of unequal length; at lanes 8 some lanes hold one stage and one none, at
+    lanes 64 most hold none), Bt = 5; and (8, 4) on the grouped layout (lanes 1), N = 3, Bt = 9,
+    whose last costate block ends on the batch's last record."""
+    import noc
+    from noc import _lib, problems
+    from noc.ipm import BatchedIPM, default_terminal
+    if name == "linear8":
+        ocp = problems.double_integrators(4, LINEAR_STEP, constrained=True)
+        rng = np.random.default_rng(13)
+        x0, u0 = 0.5 * rng.normal(size=(Bt, 8)), 0.1 * rng.normal(size=(Bt, N, 4))
+    else:
+        ocp = problems.make_problem(name, N)
+        x0, u0 = problems.initial_conditions(name, N, Bt, seed=3)
+    fam = ocp.family
+    uniform = noc.TrajectoryParams(goal=np.tile(fam.goal, (Bt, 1)), wx=fam.wx, wu=fam.wu, wf=fam.wf,
+                                   u_bound=np.full(Bt, fam.u_bound))
+    mode = _lib.MODE_PAR
+    engines = []
+    for params in (None, uniform):
+        eng = BatchedIPM(fam, N, Bt, lanes=lanes, persistent=False, overlap=False, compact=False)
+        eng.load_params(params)
+        eng.load(u0, x0)
+        eng.init()
+        engines.append(eng)
+    shared, with_params = engines
+    assert shared.t.keys() == with_params.t.keys()
+    for step in range(4):
+        for eng in engines:
+            eng.step(mode, default_terminal(mode))
+        torch.cuda.synchronize()
+        for k in shared.t:
+            assert torch.equal(_bits(shared.t[k]), _bits(with_params.t[k])), (step, k)
+    assert int(shared.t["kkt_solves"].min()) >= 1  # the steps did solve: not a comparison of zeros
+
+
 def test_cached_engine_does_not_keep_stale_parameters(monkeypatch):
     _one_wave(monkeypatch)
     from noc.par_interior_point_newton import par_interior_point_optimal_control as solve
