@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, BIG ? 1 : NOC_KKT_WAVES_PER_SIMD) void kkt_sca
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const CompactSrc<BS, NX, NU, L> src{a, prm, traj, l, cmax, (size_t)traj * a.N};
   kkt_scan_wave_src<NX, NU, L, false, true, CompactSrc<BS, NX, NU, L>, CACHE, true, BIG, false, false, false,
-                    true, KEEP>(a, traj, l, src);  // ..., no NT3, no AB, no IO0, PEEL, KEEP
+                    true, KEEP, true>(a, traj, l, src);  // ..., no NT3, no AB, no IO0, PEEL, KEEP, FOLD
 }
 
 // launch_kkt's geometry (LDS slots, waves per workgroup, the one-wave-per-SIMD instance when every

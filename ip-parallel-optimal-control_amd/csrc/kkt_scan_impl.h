@@ -328,7 +328,10 @@ NOC_DEV void prepend(Elem<NX>& e, const StageData<NX, NU>& st, double reg) {
 // The vote spans the wave, which at L < 64 holds other trajectories too: the redone solve gives a
 // lane whose own check passed the bits it already had (lu_pp_solve exchanges no row for it), so a
 // trajectory's result does not depend on its wave-mates (tests/test_kkt_neighbours_gpu.py).
-template <int NX, bool VALUE_ONLY, int SK, bool MASKED = (NX <= 2)>
+// FOLD (the stand-alone scan kernels; non-masked levels SK <= 4): the main path's fetches carry
+// the identity select inside the DPP instruction (small_linalg.h: sklansky_fetch_select), one
+// instruction per dword instead of a move and a select.  The pivoting redo re-fetches as before.
+template <int NX, bool VALUE_ONLY, int SK, bool MASKED = (NX <= 2), bool FOLD = false>
 NOC_DEV void combine_sklansky(Elem<NX>& e1) {
   const int lane = (int)__lane_id();
   // MASKED: the arithmetic under EXEC = the combining lanes; else every lane computes, the others
@@ -340,6 +343,7 @@ NOC_DEV void combine_sklansky(Elem<NX>& e1) {
   // 1.5-2.5 % slower masked and keeps the selects (profiles/r03/two_wave/)
   const bool act = MASKED ? !(lane & (1 << SK)) : true;
   const bool comb = !(lane & (1 << SK));
+  constexpr bool FSEL = FOLD && !MASKED && SK <= 4;
   auto fetch = [&](double v, double idv) {
     const double p = sklansky_rev_fetch<SK>(v, lane);
     return MASKED ? p : (comb ? p : idv);
@@ -369,7 +373,12 @@ NOC_DEV void combine_sklansky(Elem<NX>& e1) {
       }
     }
   };
-  fetch_value();
+  if constexpr (FSEL) {
+    sklansky_fetch_select<SK, false, Sym<NX>::SZ, 0>(e1.J.v, J2.v);
+    sklansky_fetch_select<SK, false, NX, 0>(e1.nu.v, nu2.v);
+  } else {
+    fetch_value();
+  }
   //  J2A1 = J2 A1,  w = nu2 + J2 b1   (e1.A, e1.b are still the pre-combine values)
   Mat<NX, NX> J2A1;
   Vec<NX> w;
@@ -419,10 +428,16 @@ NOC_DEV void combine_sklansky(Elem<NX>& e1) {
     Mat<NX, NX> A2;
     Vec<NX> b2;
     Sym<NX> C2;
-    NOC_UNROLL for (int i = 0; i < NX; ++i)
-      NOC_UNROLL for (int j = 0; j < NX; ++j) A2(i, j) = fetch(e1.A(i, j), i == j ? 1.0 : 0.0);
-    NOC_UNROLL for (int i = 0; i < NX; ++i) b2.v[i] = fetch(e1.b.v[i], 0.0);
-    NOC_UNROLL for (int i = 0; i < Sym<NX>::SZ; ++i) C2.v[i] = fetch(e1.C.v[i], 0.0);
+    if constexpr (FSEL) {
+      sklansky_fetch_select<SK, false, NX * NX, diag_bits<NX>()>(e1.A.v, A2.v);
+      sklansky_fetch_select<SK, false, NX, 0>(e1.b.v, b2.v);
+      sklansky_fetch_select<SK, false, Sym<NX>::SZ, 0>(e1.C.v, C2.v);
+    } else {
+      NOC_UNROLL for (int i = 0; i < NX; ++i)
+        NOC_UNROLL for (int j = 0; j < NX; ++j) A2(i, j) = fetch(e1.A(i, j), i == j ? 1.0 : 0.0);
+      NOC_UNROLL for (int i = 0; i < NX; ++i) b2.v[i] = fetch(e1.b.v[i], 0.0);
+      NOC_UNROLL for (int i = 0; i < Sym<NX>::SZ; ++i) C2.v[i] = fetch(e1.C.v[i], 0.0);
+    }
     if (act) {  // A = A2 TA ; b = A2 Tb + b2 ; C = A2 TC A2' + C2
       Mat<NX, NX> T2;  // A2 * TC
       NOC_UNROLL for (int i = 0; i < NX; ++i) {
@@ -451,14 +466,14 @@ NOC_DEV void combine_sklansky(Elem<NX>& e1) {
 
 // Phase 2 as a reverse Sklansky scan over an L-lane segment: log2(L) levels, partners on the VALU;
 // the last level's partner (lane L/2 of the segment) covers the terminal cost -> value-only.
-template <int NX, int L, int K = 0, bool MASKED = (NX <= 2)>
+template <int NX, int L, int K = 0, bool MASKED = (NX <= 2), bool FOLD = false>
 NOC_DEV void rev_scan_sklansky(Elem<NX>& e) {
   NOC_ISA_MARK("rev", K);
   if constexpr ((2 << K) < L) {
-    combine_sklansky<NX, false, K, MASKED>(e);
-    rev_scan_sklansky<NX, L, K + 1, MASKED>(e);
+    combine_sklansky<NX, false, K, MASKED, FOLD>(e);
+    rev_scan_sklansky<NX, L, K + 1, MASKED, FOLD>(e);
   } else if constexpr ((2 << K) == L) {
-    combine_sklansky<NX, true, K, MASKED>(e);
+    combine_sklansky<NX, true, K, MASKED, FOLD>(e);
     NOC_ISA_MARK("rev", K + 1);
   }
 }
@@ -648,9 +663,15 @@ constexpr int keep_rec_doubles() {
 // which it does not depend on.  Phase 3's loop then runs over the wave-uniform slot (lanes with the
 // shorter chunk sit out its first pass instead of its last), so the buffer is indexed by a scalar
 // and stays in registers.  Off (0) everywhere else: the one-stage hand-off above.
+// FOLD (the stand-alone scan kernels): the non-masked scan levels of phases 2 and 4 fetch their
+// partners with the identity select folded into the DPP instruction (combine_sklansky,
+// sklansky_fwd_level): the same bits in half the fetch instructions.  On for nx <= 4 (the 256-
+// register nx = 4 instances; nx <= 2 and the 512-register instances are masked and have no select
+// to fold); the nx = 8 instances, whose elements live in scratch, and the persistent solvers
+// compile exactly what they compiled without it.
 template <int NX, int NU, int L, bool AFF, bool TILED, class SRC, int CACHE = 0, bool HANDOFF = true,
           bool BIG = false, bool NT3 = false, bool AB = (BIG && ab_supported<NX, NU>()), bool IO0 = false,
-          bool PEEL = false, int KEEP = 0>
+          bool PEEL = false, int KEEP = 0, bool FOLD = false>
 NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, const SRC& src) {
   constexpr int KD = kd_width<NX, NU>();
   using ST = typename SRC::Struct;  // structural zeros of A, B (DenseBlocks: none)
@@ -755,7 +776,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     NOC_STAMP(1); NOC_ISA_MARK("phase", 1);
     // ---------------- phase 2: reverse Sklansky scan across lanes ----------------
     if constexpr (W == 1) {
-      if (!(a.ablate & 1)) rev_scan_sklansky<NX, L, 0, (NX <= 2 || BIG)>(e);
+      if (!(a.ablate & 1)) rev_scan_sklansky<NX, L, 0, (NX <= 2 || BIG), FOLD>(e);
     } else {
       if (!(a.ablate & 1)) {
         // per wave; wave 1 ends at the terminal cost (value-only last level), wave 0 at wave 1's
@@ -1106,7 +1127,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     }
   }
   (void)kept;
-  affine_prefix_sklansky<NX, LW>(Phi, phi);  // partners on the VALU (small_linalg.h)
+  affine_prefix_sklansky<NX, LW, FOLD>(Phi, phi);  // partners on the VALU (small_linalg.h)
   Vec<NX> x;
   wave_shift_up1<NX>(phi.v, x.v);  // lane l-1's prefix; segment starts: x0 / the join below
   if (l == 0) x = x0;
@@ -1326,7 +1347,7 @@ NOC_DEV void kkt_scan_wave(const KKTArgs& a, const int traj, const int l) {
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const ArgsSrc<NX, NU, L, AFF, TILED> src{a, traj, l, cmax, (size_t)traj * a.N};
   kkt_scan_wave_src<NX, NU, L, AFF, TILED, ArgsSrc<NX, NU, L, AFF, TILED>, CACHE, HANDOFF, BIG, NT3,
-                    (BIG && ab_supported<NX, NU>()), false, true>(a, traj, l, src);
+                    (BIG && ab_supported<NX, NU>()), false, true, 0, (NX <= 4)>(a, traj, l, src);  // PEEL, no KEEP, FOLD
 }
 
 // BIG (L = 32, 64; nx = 3, 4): one wave per SIMD -- for batches whose waves all fit one per SIMD

@@ -342,6 +342,110 @@ NOC_DEV double sklansky_rev_fetch(double v, int lane) {
     return readlane_dbl(v, 32);
   }
 }
+// The same fetches for a scan level whose every lane computes (the non-masked levels): the lanes
+// that do not combine at level K receive the identity element's dword instead of a partner's.
+// Fetch and select are ONE instruction per dword, v_cndmask_b32 with a DPP source
+// (D = VCC ? src1 : dpp(src0)): src1 = the identity dword in a VGPR, VCC = the lanes that do not
+// combine, a constant of the level.  The compiler emits a DPP move and a separate select (the
+// identity as an inline constant, the mask in an SGPR pair: neither fits the VOP2 DPP form), so
+// the instruction is written out, up to four doubles per statement.  Each statement opens with
+// the VCC move and s_nop 1: three wait states between any VALU write of a source (the level-4
+// row swap's included) and the first DPP read, where the hardware asks for two.  Level 2's two
+// source lanes per row take a second, bank-masked DPP move over the selected result (the banks it
+// writes are combining ones); level 4 applies the select to the row broadcast that follows
+// v_permlane16_swap.  K <= 4 only: the level-5 fetch is a v_readlane, whose select has an SGPR
+// source already.  Moves and selects only: every lane gets the bits of fetch-then-select.
+template <int N>
+constexpr unsigned long long diag_bits() {  // the diagonal of a row-major Mat<N, N>, N <= 8
+  static_assert(N * N <= 64, "one bit per entry");
+  unsigned long long m = 0;
+  for (int i = 0; i < N; ++i) m |= 1ull << (i * N + i);
+  return m;
+}
+template <int K, bool FWD>
+constexpr unsigned long long sklansky_keep_mask() {
+  unsigned long long m = 0;
+  for (int l = 0; l < 64; ++l)
+    if ((((l >> K) & 1) != 0) != FWD) m |= 1ull << l;
+  return m;
+}
+#define NOC_FSEL_SEL(n, C)                                                                     \
+  "v_cndmask_b32_dpp %[d" #n "], %[s" #n "], %[i" #n "], vcc " C " row_mask:0xf bank_mask:0xf\n\t"
+#define NOC_FSEL_MOV(n, C, BK) \
+  "v_mov_b32_dpp %[d" #n "], %[s" #n "] " C " row_mask:0xf bank_mask:" BK "\n\t"
+#define NOC_FSEL_R0(n) NOC_FSEL_SEL(n, "quad_perm:[1,1,3,3]")
+#define NOC_FSEL_R1(n) NOC_FSEL_SEL(n, "quad_perm:[2,2,2,2]")
+#define NOC_FSEL_R2(n) NOC_FSEL_SEL(n, "row_newbcast:4") NOC_FSEL_MOV(n, "row_newbcast:12", "0x4")
+#define NOC_FSEL_R3(n) NOC_FSEL_SEL(n, "row_newbcast:8")
+#define NOC_FSEL_R4(n) NOC_FSEL_SEL(n, "row_newbcast:0")
+#define NOC_FSEL_F0(n) NOC_FSEL_SEL(n, "quad_perm:[0,0,2,2]")
+#define NOC_FSEL_F1(n) NOC_FSEL_SEL(n, "quad_perm:[1,1,1,1]")
+#define NOC_FSEL_F2(n) NOC_FSEL_SEL(n, "row_newbcast:3") NOC_FSEL_MOV(n, "row_newbcast:11", "0x8")
+#define NOC_FSEL_F3(n) NOC_FSEL_SEL(n, "row_newbcast:7")
+#define NOC_FSEL_F4(n) NOC_FSEL_SEL(n, "row_newbcast:15")
+#define NOC_FSEL_OUT(n) [d##n] "=&v"(d[n])
+#define NOC_FSEL_IN(n) [s##n] "v"(s[n]), [i##n] "v"(id[n])
+#define NOC_FSEL_REP2(X) X(0) X(1)
+#define NOC_FSEL_REP4(X) NOC_FSEL_REP2(X) X(2) X(3)
+#define NOC_FSEL_REP8(X) NOC_FSEL_REP4(X) X(4) X(5) X(6) X(7)
+#define NOC_FSEL_LIST2(X) X(0), X(1)
+#define NOC_FSEL_LIST4(X) NOC_FSEL_LIST2(X), X(2), X(3)
+#define NOC_FSEL_LIST8(X) NOC_FSEL_LIST4(X), X(4), X(5), X(6), X(7)
+#define NOC_FSEL_ASM(W, X)                                          \
+  asm("s_mov_b64 vcc, %[m]\n\ts_nop 1\n\t" NOC_FSEL_REP##W(X)       \
+      : NOC_FSEL_LIST##W(NOC_FSEL_OUT)                              \
+      : NOC_FSEL_LIST##W(NOC_FSEL_IN), [m] "s"(m)                   \
+      : "vcc")
+#define NOC_FSEL_LEVELS(W)                                           \
+  if constexpr (!FWD && K == 0) NOC_FSEL_ASM(W, NOC_FSEL_R0);        \
+  else if constexpr (!FWD && K == 1) NOC_FSEL_ASM(W, NOC_FSEL_R1);   \
+  else if constexpr (!FWD && K == 2) NOC_FSEL_ASM(W, NOC_FSEL_R2);   \
+  else if constexpr (!FWD && K == 3) NOC_FSEL_ASM(W, NOC_FSEL_R3);   \
+  else if constexpr (!FWD && K == 4) NOC_FSEL_ASM(W, NOC_FSEL_R4);   \
+  else if constexpr (FWD && K == 0) NOC_FSEL_ASM(W, NOC_FSEL_F0);    \
+  else if constexpr (FWD && K == 1) NOC_FSEL_ASM(W, NOC_FSEL_F1);    \
+  else if constexpr (FWD && K == 2) NOC_FSEL_ASM(W, NOC_FSEL_F2);    \
+  else if constexpr (FWD && K == 3) NOC_FSEL_ASM(W, NOC_FSEL_F3);    \
+  else NOC_FSEL_ASM(W, NOC_FSEL_F4)
+// CNT doubles src -> dst; bit i of ONES: double i's identity value is 1.0 (else 0.0)
+template <int K, bool FWD, int CNT, unsigned long long ONES>
+NOC_DEV void sklansky_fetch_select(const double* src, double* dst) {
+  static_assert(K >= 0 && K <= 4, "levels fetched by DPP");
+  constexpr int ND = CNT >= 4 ? 4 : (CNT >= 2 ? 2 : 1);  // doubles of this statement
+  constexpr int W = 2 * ND;
+  if constexpr (CNT > 0) {
+    const unsigned long long m = sklansky_keep_mask<K, FWD>();
+    int s[W], id[W], d[W];
+    NOC_UNROLL for (int i = 0; i < ND; ++i) {
+      s[2 * i] = __double2loint(src[i]);
+      s[2 * i + 1] = __double2hiint(src[i]);
+      id[2 * i] = 0;
+      id[2 * i + 1] = ((ONES >> i) & 1) ? 0x3FF00000 : 0;
+    }
+    if constexpr (K == 4) {  // the xor-16 row first (permrow_bcast)
+      NOC_UNROLL for (int i = 0; i < W; ++i) {
+        const auto r = __builtin_amdgcn_permlane16_swap(s[i], s[i], false, false);
+        s[i] = FWD ? (int)r[0] : (int)r[1];
+      }
+    }
+    if constexpr (W == 8) { NOC_FSEL_LEVELS(8); }
+    else if constexpr (W == 4) { NOC_FSEL_LEVELS(4); }
+    else { NOC_FSEL_LEVELS(2); }
+    NOC_UNROLL for (int i = 0; i < ND; ++i) dst[i] = __hiloint2double(d[2 * i + 1], d[2 * i]);
+    sklansky_fetch_select<K, FWD, CNT - ND, (ONES >> ND)>(src + ND, dst + ND);
+  }
+}
+#undef NOC_FSEL_LEVELS
+#undef NOC_FSEL_ASM
+#undef NOC_FSEL_LIST8
+#undef NOC_FSEL_LIST4
+#undef NOC_FSEL_LIST2
+#undef NOC_FSEL_REP8
+#undef NOC_FSEL_REP4
+#undef NOC_FSEL_REP2
+#undef NOC_FSEL_IN
+#undef NOC_FSEL_OUT
+
 // Butterfly all-reduce over an L-lane segment on the VALU, bit-identical to the __shfl_xor loop
 // `for (off = L/2; off; off >>= 1) v = op(v, shfl_xor(v, off))`: the xor-32 / xor-16 partners
 // by v_permlane32_swap / v_permlane16_swap, xor-8 by row_ror:8, xor-4 by row_ror:12 (lane i <-
@@ -397,7 +501,9 @@ NOC_DEV void segment_sum_and(double& sum, int& all, int lane) {
 // Level K of the inclusive prefix of affine maps x -> Phi x + phi: the upper half of every aligned
 // 2^(K+1)-lane block composes its map with the lower half's last prefix (under EXEC: the other
 // lanes keep theirs exactly).
-template <int K, int NX, int L>
+// FOLD (the stand-alone scan kernels): the non-masked levels K <= 4 fetch with the identity select
+// folded into the DPP instruction (sklansky_fetch_select) -- the same bits, half the instructions.
+template <int K, int NX, int L, bool FOLD = false>
 NOC_DEV void sklansky_fwd_level(Mat<NX, NX>& Phi, Vec<NX>& phi, int lane) {
   if constexpr ((1 << K) < L) {
     // MASKED (small nx): the composition runs under EXEC = the combining lanes; larger nx compose
@@ -406,13 +512,18 @@ NOC_DEV void sklansky_fwd_level(Mat<NX, NX>& Phi, Vec<NX>& phi, int lane) {
     const bool comb = (lane & (1 << K)) != 0;
     Mat<NX, NX> oP;
     Vec<NX> op;
-    NOC_UNROLL for (int i = 0; i < NX; ++i) {
-      NOC_UNROLL for (int j = 0; j < NX; ++j) {
-        const double p = sklansky_fwd_fetch<K>(Phi(i, j), lane);
-        oP(i, j) = (MASKED || comb) ? p : (i == j ? 1.0 : 0.0);
+    if constexpr (FOLD && !MASKED && K <= 4) {
+      sklansky_fetch_select<K, true, NX * NX, diag_bits<NX>()>(Phi.v, oP.v);
+      sklansky_fetch_select<K, true, NX, 0>(phi.v, op.v);
+    } else {
+      NOC_UNROLL for (int i = 0; i < NX; ++i) {
+        NOC_UNROLL for (int j = 0; j < NX; ++j) {
+          const double p = sklansky_fwd_fetch<K>(Phi(i, j), lane);
+          oP(i, j) = (MASKED || comb) ? p : (i == j ? 1.0 : 0.0);
+        }
+        const double p = sklansky_fwd_fetch<K>(phi[i], lane);
+        op[i] = (MASKED || comb) ? p : 0.0;
       }
-      const double p = sklansky_fwd_fetch<K>(phi[i], lane);
-      op[i] = (MASKED || comb) ? p : 0.0;
     }
     if (!MASKED || comb) {
       Mat<NX, NX> Pn;
@@ -430,22 +541,22 @@ NOC_DEV void sklansky_fwd_level(Mat<NX, NX>& Phi, Vec<NX>& phi, int lane) {
     }
   }
 }
-template <int NX, int L>
+template <int NX, int L, bool FOLD = false>
 NOC_DEV void affine_prefix_sklansky(Mat<NX, NX>& Phi, Vec<NX>& phi) {
   static_assert(L >= 1 && L <= 64 && (L & (L - 1)) == 0, "segment width: a power of two <= 64");
   const int lane = (int)__lane_id();
   NOC_ISA_MARK("fwd", 0);
-  sklansky_fwd_level<0, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<0, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 1);
-  sklansky_fwd_level<1, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<1, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 2);
-  sklansky_fwd_level<2, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<2, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 3);
-  sklansky_fwd_level<3, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<3, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 4);
-  sklansky_fwd_level<4, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<4, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 5);
-  sklansky_fwd_level<5, NX, L>(Phi, phi, lane);
+  sklansky_fwd_level<5, NX, L, FOLD>(Phi, phi, lane);
   NOC_ISA_MARK("fwd", 6);
 }
 

@@ -5,7 +5,10 @@ with -DNOC_ISA_MARKS: assembler comments at every scan level and phase boundary)
   python tools/isa_levels.py <file.s> <kernel-substring>   (e.g. 'ILi2ELi1ELi64ELb0ELb1ELi2E')
 
 Counts, between consecutive markers of the kernel: all instructions, VALU (v_*), fp64 FMA/MUL/ADD,
-DPP movs, v_readlane, LDS (ds_*), divisions (v_div_scale_f64 = one fp64 division), waits."""
+DPP instructions, v_readlane, v_permlane*, selects (v_cndmask_b32 alone / with a DPP source),
+scratch accesses, LDS (ds_*), divisions (v_div_scale_f64 = one fp64 division), waits.  The markers
+are positions in the emitted code: the scheduler moves instructions across them, so a level's
+first fetches may be counted in the segment before it (sum neighbouring segments to compare)."""
 import re
 import sys
 
@@ -40,6 +43,11 @@ def stats(ops):
     return dict(total=len(ops), valu=sum(o.startswith("v_") for o in ops),
                 f64=sum(o.endswith("_f64") for o in ops),
                 dpp=sum("dpp" in o for o in ops), readlane=sum("readlane" in o for o in ops),
+                permlane=sum(o.startswith("v_permlane") for o in ops),
+                # selects on their own, and selects folded into a DPP fetch (counted in dpp too)
+                sel=sum(o.startswith("v_cndmask") and "dpp" not in o for o in ops),
+                seldpp=sum(o.startswith("v_cndmask") and "dpp" in o for o in ops),
+                scratch=sum(o.startswith("scratch_") for o in ops),
                 lds=sum(o.startswith("ds_") for o in ops),
                 div=sum(o.startswith("v_div_scale_f64") for o in ops) // 2,
                 rcp=sum(o.startswith("v_rcp_f64") for o in ops),
