@@ -58,9 +58,15 @@ struct GenPattern {
   static constexpr bool kLinear = KIND == NOC_FAMILY_LINEAR;
   static constexpr bool kDiscrete = Fam<KIND, NX, NU>::kDiscrete;
   static constexpr bool kGenCost = Fam<KIND, NX, NU>::kGenCost;
+  // The generated patterns are the ODE's.  Under RK4 they are not the stage map's: a constant ODE
+  // Jacobian entry (cart-pole's row xdot = v) picks up state-dependent terms through k_1 .. k_3,
+  // and structural zeros of the ODE Hessian fill in the same way, so every entry of A, B and of
+  // the dynamics Hessian counts as variable (the traced-cost patterns below are unaffected).
+  static constexpr bool kRk4 = Fam<KIND, NX, NU>::kRk4;
   // ODE (or discrete map) Jacobian entry k of [fx | fu] (row-major NX x NZ)
   static constexpr bool jvar(int k) {
-    if constexpr (KIND == NOC_FAMILY_PENDULUM) return gen::pendulum_jac_var[k] != 0;
+    if constexpr (kRk4) return true;
+    else if constexpr (KIND == NOC_FAMILY_PENDULUM) return gen::pendulum_jac_var[k] != 0;
     else if constexpr (KIND == NOC_FAMILY_CARTPOLE) return gen::cartpole_jac_var[k] != 0;
 #ifdef NOC_CUSTOM_FAMILY
     else if constexpr (KIND == NOC_FAMILY_CUSTOM) return gen::custom_jac_var[k] != 0;
@@ -77,7 +83,8 @@ struct GenPattern {
   }
   // lambda-contracted Hessian entry k (NZ x NZ) not identically zero
   static constexpr bool hnz(int k) {
-    if constexpr (kLinear) return false;
+    if constexpr (kRk4) return true;
+    else if constexpr (kLinear) return false;
     else if constexpr (KIND == NOC_FAMILY_PENDULUM) return gen::pendulum_hess_nz[k] != 0;
     else if constexpr (KIND == NOC_FAMILY_CARTPOLE) return gen::cartpole_hess_nz[k] != 0;
 #ifdef NOC_CUSTOM_FAMILY

@@ -12,6 +12,7 @@
 #include "families_gen.h"
 #include "noc_internal.h"
 #include "small_linalg.h"
+#include "rk4_map.h"
 #ifdef NOC_CUSTOM_FAMILY
 // a custom-family build (noc.families.register_family): the generated ODE / discrete map of the
 // registered problem, its Jacobian and lambda-contracted Hessian (noc/_codegen.py), found first
@@ -22,6 +23,17 @@
 namespace noc {
 
 constexpr double kTwoPi = 6.283185307179586;  // 2.0 * jnp.pi
+
+// How a family's ODE becomes its stage map: one explicit Euler step (noc/utils.py:50-54) or one
+// classical Runge-Kutta step (noc/utils.py:13-23, rk4_map.h).  A compile-time property of a
+// registered family's library: its generated header sets gen::kCustomIntegrator for RK4
+// (register_family(integrator="rk4")) and says nothing for Euler, which the unqualified lookup
+// below then finds here, one namespace up.
+constexpr int kIntegratorEuler = 0, kIntegratorRk4 = 1;
+constexpr int kCustomIntegrator = kIntegratorEuler;
+namespace gen {
+constexpr int custom_integrator() { return kCustomIntegrator; }
+}  // namespace gen
 
 // noc/utils.py:8-10 with jnp.remainder semantics (C fmod, + divisor if the sign differs).
 // fmod is exact, and so is its value on the two innermost periods: fmod(a, 2 pi) == a for
@@ -54,9 +66,13 @@ struct Fam {
   // (noc.families.register_family(stage_cost=..., final_cost=..., constraints=...)), instead of
   // the parametrised quadratic tracking cost with a box log barrier on u
   static constexpr bool kGenCost = (KIND == NOC_FAMILY_CUSTOM) && gen::kCustomCost;
+  // the ODE is discretised with one RK4 step per stage (rk4_map.h) instead of Euler's
+  static constexpr bool kRk4 = (KIND == NOC_FAMILY_CUSTOM) && !gen::kCustomDiscrete &&
+                               gen::custom_integrator() == kIntegratorRk4;
 #else
   static constexpr bool kDiscrete = false;
   static constexpr bool kGenCost = false;
+  static constexpr bool kRk4 = false;
 #endif
   // generated right-hand side / Jacobian J = d rhs / d[x; u] / lambda-contracted Hessian
   NOC_DEV static void rhs(const double* x, const double* u, double* f) {
@@ -92,6 +108,8 @@ struct Fam {
       }
     } else if constexpr (kDiscrete) {
       rhs(x, u, xn);
+    } else if constexpr (kRk4) {
+      rk4::step<Fam, NX, NU>(p.dt, x, u, xn);
     } else {
       double f[NX];
       rhs(x, u, f);
@@ -102,6 +120,8 @@ struct Fam {
     if constexpr (KIND == NOC_FAMILY_LINEAR) {
       NOC_UNROLL for (int i = 0; i < NX * NX; ++i) fx[i] = p.A[i];
       NOC_UNROLL for (int i = 0; i < NX * NU; ++i) fu[i] = p.B[i];
+    } else if constexpr (kRk4) {
+      rk4::jac<Fam, NX, NU>(p.dt, x, u, fx, fu);
     } else {
       constexpr int NZ = NX + NU;
       double J[NX * NZ];
@@ -117,10 +137,13 @@ struct Fam {
       }
     }
   }
-  // sum_i lam_i d2 f_i (Euler: dt * ode Hessians); adds into Hxx (NXxNX), Huu, Hxu (NXxNU)
+  // sum_i lam_i d2 f_i (Euler: dt * ode Hessians; RK4: the second-order adjoint of the four
+  // evaluations); adds into Hxx (NXxNX), Huu, Hxu (NXxNU)
   NOC_DEV void add_hess_l(const double* x, const double* u, const double* lam, double* Hxx,
                           double* Huu, double* Hxu) const {
-    if constexpr (KIND != NOC_FAMILY_LINEAR) {
+    if constexpr (kRk4) {
+      rk4::add_hess_l<Fam, NX, NU>(p.dt, x, u, lam, Hxx, Huu, Hxu);
+    } else if constexpr (KIND != NOC_FAMILY_LINEAR) {
       constexpr int NZ = NX + NU;
       double H[NZ * NZ];
       rhs_hess_l(x, u, lam, H);

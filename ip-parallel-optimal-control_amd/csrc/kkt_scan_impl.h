@@ -32,8 +32,15 @@
 // The scan is compiled with cross-statement FMA contraction (the library default is
 // -ffp-contract=on, which keeps the interior-point drivers' arithmetic independent of inlining
 // context); every kernel that inlines this scan sees the same pragma, so the standalone and the
-// persistent KKT solves still round identically.
+// persistent KKT solves still round identically -- where the backend makes the same choice in both
+// copies: under `fast` it chooses per inlined copy (small_linalg.h: opaque).  A library built with
+// -DNOC_SCAN_CONTRACT_ON keeps the scan at the library default instead, so every fusion is the
+// front end's, the same in every copy.
+#ifdef NOC_SCAN_CONTRACT_ON
+#pragma clang fp contract(on)
+#else
 #pragma clang fp contract(fast)
+#endif
 
 #ifndef NOC_KKT_WAVES_PER_SIMD
 #define NOC_KKT_WAVES_PER_SIMD 2
