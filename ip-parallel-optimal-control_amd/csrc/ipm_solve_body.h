@@ -378,8 +378,7 @@
       // traffic -- c3 ipm_solve -2.4 %, c2 -1 %, bit-identical (profiles/r05/handoff_persist/)
       {
         const CompactSrc<BS, NX, NU, PL> src{a, prm, b, l, cmax, (size_t)b * N};
-        kkt_scan_wave_src<NX, NU, PL, false, true, CompactSrc<BS, NX, NU, PL>, 0, true, false, false, false,
-                          (SPEC > 1)>(a, b, l, src);
+        kkt_scan_wave_src<NX, NU, PL, false, true, CompactSrc<BS, NX, NU, PL>, ScanOptIO0<(SPEC > 1)>>(a, b, l, src);
       }
       wave_fence();  // pred / feasible written by lane 0
       sol = *state_slot<NX, NU>(N, SPEC, wv);

@@ -33,10 +33,8 @@ struct CompactSrc {
   }
   // PART / LAST: as load_stage (kkt_scan_impl.h)
   template <int PART, bool LAST = false>
-  NOC_DEV void stage_part(int s, int j, double reg, StageData<NX, NU>& st) const {
+  NOC_DEV void stage_part(int, int j, StageData<NX, NU>& st) const {
     constexpr bool REST = PART != 2, WQ = PART != 1, WAB = REST && PART != 3;
-    (void)s;
-    (void)reg;
     if constexpr (WAB) {
       field<BF_A>(a.A, j, st.A.v);
       field<BF_B>(a.Bm, j, st.B.v);
@@ -48,12 +46,9 @@ struct CompactSrc {
       tload_pol<NU, L, LAST>(a.r, traj, j, l, cmax, st.r.v);
     }
   }
-  NOC_DEV void stage(int s, int j, double reg, StageData<NX, NU>& st) const { stage_part<0>(s, j, reg, st); }
-  NOC_DEV void stage_last(int s, int j, double reg, StageData<NX, NU>& st) const {
-    stage_part<0, true>(s, j, reg, st);
-  }
-  NOC_DEV void ab(int s, int j, Mat<NX, NX>& A, Mat<NX, NU>& Bm, Vec<NX>& c) const {
-    (void)s;
+  NOC_DEV void stage(int s, int j, StageData<NX, NU>& st) const { stage_part<0>(s, j, st); }
+  NOC_DEV void stage_last(int s, int j, StageData<NX, NU>& st) const { stage_part<0, true>(s, j, st); }
+  NOC_DEV void ab(int, int j, Mat<NX, NX>& A, Mat<NX, NU>& Bm, Vec<NX>& c) const {
     field<BF_A, true>(a.A, j, A.v);  // phase 4: the last read of A, B (non-temporal)
     field<BF_B, true>(a.Bm, j, Bm.v);
     set_zero(c);
@@ -75,11 +70,18 @@ struct CompactSrc {
   }
 };
 
+// kkt_scan_compact_kernel's options, from its template parameters: kkt_scan_kernel's, with the kept
+// slots, without the A, B slots in LDS and the non-temporal phase 3 (the compact blocks of the
+// batches those exist for stay within the memory-side cache)
+template <int CACHE_, bool BIG_, int KEEP_>
+struct CompactKernelOpt : ScanOpt {
+  static constexpr int CACHE = CACHE_, KEEP = KEEP_;
+  static constexpr bool BIG = BIG_, AB = false, PEEL = true, FOLD = true;
+};
+
 // The stand-alone scan on compact blocks: kkt_scan_kernel's tiled, non-affine instance with the
 // blocks read through CompactSrc (a.A, a.Bm, a.Q, a.R, a.M: the compact fields).  Same dead-wave /
-// barrier prologue, same register budgets (BIG: one wave per SIMD); no A, B slots in LDS and no
-// non-temporal phase-3 instance (the compact blocks of the batches those exist for stay within the
-// memory-side cache).
+// barrier prologue, same register budgets (BIG: one wave per SIMD).
 template <int KIND, int NX, int NU, int L, int CACHE, bool BIG, int KEEP = 0>
 __global__ __launch_bounds__(256, BIG ? 1 : NOC_KKT_WAVES_PER_SIMD) void kkt_scan_compact_kernel(noc_family prm,
                                                                                              KKTArgs a) {
@@ -87,44 +89,27 @@ __global__ __launch_bounds__(256, BIG ? 1 : NOC_KKT_WAVES_PER_SIMD) void kkt_sca
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   if constexpr (BIG) asm volatile("" ::: "a255");  // the whole register file, as kkt_scan_kernel
   const int traj = tid / L;
-  // a wave without a live trajectory still meets its block's one copy-out barrier (kkt_scan_kernel)
-  const bool dead = traj >= a.B || (a.active && a.active[traj] == 0);
-  const bool wave_live = __any(!dead);  // voted at the wave's full EXEC, before any branch
-  if (dead) {
-    if (!wave_live && a.lds_out && a.mode != MODE_BWD && !(a.ablate & 6)) __syncthreads();
-    return;
-  }
+  if (!scan_lane_live(a, traj)) return;
   using BS = BlockStruct<KIND, NX, NU, true>;
   const int l = tid % L;
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const CompactSrc<BS, NX, NU, L> src{a, prm, traj, l, cmax, (size_t)traj * a.N};
-  kkt_scan_wave_src<NX, NU, L, false, true, CompactSrc<BS, NX, NU, L>, CACHE, true, BIG, false, false, false,
-                    true, KEEP, true>(a, traj, l, src);  // ..., no NT3, no AB, no IO0, PEEL, KEEP, FOLD
+  kkt_scan_wave_src<NX, NU, L, false, true, CompactSrc<BS, NX, NU, L>, CompactKernelOpt<CACHE, BIG, KEEP>>(a, traj, l,
+                                                                                                            src);
 }
 
-// launch_kkt's geometry (LDS slots, waves per workgroup, the one-wave-per-SIMD instance when every
-// wave of the batch fits one per SIMD, the register-cached chunk of short nx = 2 chunks) for the
-// compact kernel; the A, B slots stay off.  Instantiated per (family, lanes) in kkt_scan_compact_*.hip.
+// launch_kkt's geometry (kkt_launch_geometry) for the compact kernel; the A, B slots stay off.
+// Instantiated per (family, lanes) in kkt_scan_compact_*.hip.
 template <int KIND, int NX, int NU, int L>
 hipError_t launch_kkt_compact(const noc_family& prm, const KKTArgs& a_in, hipStream_t stream) {
+  static_assert(L <= 64, "one-wave segments");
   KKTArgs a = a_in;
-  const long long threads = (long long)a.B * L;
   constexpr int CC = kkt_cache_len<NX, NU, L>();
-  const int cmax = a.N / L + (a.N % L ? 1 : 0);
-  const bool cached = CC > 0 && cmax <= CC && !(a.ablate & 8);
-  constexpr bool kHasBig = (L == 64 || L == 32) && NX >= 3 && NX <= 4;
+  constexpr bool kHasBig = (L == 64 || L == 32) && NX >= 3 && NX <= 4;  // (kkt_launch_geometry: big)
   constexpr int KP = compact_keep(KIND, L);  // the streamed instances' kept slots (block_struct.h)
-  const bool big = kHasBig && (threads + 63) / 64 <= kkt_device_simds() && kkt_big_enabled();
-  const size_t slots1 = (a.mode == MODE_BWD || (!a.dx && !a.du)) ? 0 : kkt_lds_bytes_rt(NX, NU, a.N, L);
-  const int wpb = kkt_waves_per_block((threads + 63) / 64, slots1);
-  const size_t lds = slots1 * wpb;
-  a.lds_out = slots1 > 0 ? 1 : 0;
-  a.ab_slots = 0;
-  a.lds_base = 0;
+  const auto [cached, big, lds, block, grid, ok] = kkt_launch_geometry<NX, NU, L, false>(a);
   a.tiled = 1;
-  const int block = 64 * wpb;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
-  if (!a.lds_out && (!a.K || !a.d)) return hipErrorInvalidValue;  // K/d needed as workspace
+  if (!ok) return hipErrorInvalidValue;  // K/d needed as workspace
   if (cached) {
     if constexpr (CC > 0)
       hipLaunchKernelGGL((kkt_scan_compact_kernel<KIND, NX, NU, L, CC, false>), dim3(grid), dim3(block), lds, stream,

@@ -133,8 +133,7 @@ NOC_DEV void tload_pol(const double* __restrict__ base, int traj, int j, int l, 
 // they bring in do not displace blocks still to be re-read (other waves' chunks, this wave's A,
 // B, c for phase 4) from the memory-side cache; A, B, c keep the default policy
 template <int NX, int NU, int L, bool AFF, bool TILED, int PART = 0, bool LAST = false>
-NOC_DEV void load_stage(const KKTArgs& a, int traj, size_t si, int j, int l, int cmax, double reg,
-                        StageData<NX, NU>& st) {
+NOC_DEV void load_stage(const KKTArgs& a, int traj, size_t si, int j, int l, int cmax, StageData<NX, NU>& st) {
   constexpr bool REST = PART != 2, WQ = PART != 1, WAB = REST && PART != 3;
   if constexpr (TILED) {
     if constexpr (WAB) {
@@ -167,10 +166,6 @@ NOC_DEV void load_stage(const KKTArgs& a, int traj, size_t si, int j, int l, int
       }
     }
   }
-  // reg is NOT added here: R + reg*I is formed where R is first used (prepend / riccati_stage),
-  // so no arithmetic waits on the R load right after it is issued and a stage's loads can be
-  // prefetched a stage ahead (phase 3)
-  (void)reg;
 }
 
 // A, B (and c) of one stage for the forward pass / map composition
@@ -213,6 +208,9 @@ NOC_DEV void load_Kd(const KKTArgs& a, int traj, size_t si, int j, int l, int cm
 }
 
 // e <- stage (x) e   (Riccati-form prepend of one stage to the chunk element)
+// R + reg I is formed here and in riccati_stage, where R is first used, not where the stage is
+// loaded: no arithmetic then waits on the R load right after it is issued, and a stage's loads can
+// be issued ahead of the stage that uses them.
 template <int NX, int NU, bool AFF, class ST = DenseBlocks<NX, NU>>
 NOC_DEV void prepend(Elem<NX>& e, const StageData<NX, NU>& st, double reg) {
   Mat<NX, NX> JA;
@@ -612,15 +610,15 @@ struct ArgsSrc {
   const KKTArgs& a;
   int traj, l, cmax;
   size_t tN;
-  NOC_DEV void stage(int s, int j, double reg, StageData<NX, NU>& st) const {
-    load_stage<NX, NU, L, AFF, TILED>(a, traj, tN + s, j, l, cmax, reg, st);
+  NOC_DEV void stage(int s, int j, StageData<NX, NU>& st) const {
+    load_stage<NX, NU, L, AFF, TILED>(a, traj, tN + s, j, l, cmax, st);
   }
   template <int PART, bool LAST = false>
-  NOC_DEV void stage_part(int s, int j, double reg, StageData<NX, NU>& st) const {
-    load_stage<NX, NU, L, AFF, TILED, PART, LAST>(a, traj, tN + s, j, l, cmax, reg, st);
+  NOC_DEV void stage_part(int s, int j, StageData<NX, NU>& st) const {
+    load_stage<NX, NU, L, AFF, TILED, PART, LAST>(a, traj, tN + s, j, l, cmax, st);
   }
-  NOC_DEV void stage_last(int s, int j, double reg, StageData<NX, NU>& st) const {  // phase 3
-    load_stage<NX, NU, L, AFF, TILED, 0, true>(a, traj, tN + s, j, l, cmax, reg, st);
+  NOC_DEV void stage_last(int s, int j, StageData<NX, NU>& st) const {  // phase 3
+    load_stage<NX, NU, L, AFF, TILED, 0, true>(a, traj, tN + s, j, l, cmax, st);
   }
   NOC_DEV void ab(int s, int j, Mat<NX, NX>& A, Mat<NX, NU>& Bm, Vec<NX>& c) const {
     load_AB<NX, NU, L, AFF, TILED>(a, traj, tN + s, j, l, cmax, A, Bm, c);
@@ -639,47 +637,71 @@ constexpr int keep_rec_doubles() {
   else return 1;
 }
 
+// Compile-time options of kkt_scan_wave_src and their defaults; a caller derives and overrides.
+struct ScanOpt {
+  // CACHE > 0 (caller guarantees every chunk has <= CACHE stages): the lane's chunk is loaded into
+  // registers once, all loads issued up front, and phases 1, 3 and 4 read it from there -- one
+  // pass over the blocks and one exposed memory latency instead of three dependent load chains
+  // (small nx with one- or two-stage chunks, c2).
+  static constexpr int CACHE = 0;
+  // phase 3 hands the chunk's first stage (A, B) to phase 4 in registers (standalone scan: -1
+  // stage of phase 4's re-reads); also inside the persistent solver since round 5, whose solve is
+  // bound by its workspace traffic (profiles/r05/handoff_persist/).
+  static constexpr bool HANDOFF = true;
+  // the instance owns a SIMD (512 registers): the combines run masked (no identity partner).
+  static constexpr bool BIG = false;
+  // phase 3's re-read of a stage, the last use of Q, R, M, r, q, is non-temporal (kkt_nt3).
+  static constexpr bool NT3 = false;
+  // A, B of chunk slots j < a.ab_slots stay in LDS from phase 1 to phases 3 and 4 (lds_ab);
+  // a.ab_slots = 0 turns it off at run time.  Takes effect only in the BIG instances of a shape
+  // ab_supported (the 512-register L = 32 / 64 instances, where one wave per SIMD leaves 40 KB of
+  // LDS per wave: scan_ab below).  Not in the two-wave segments (L = 128): their re-reads are L2
+  // hits already, and the slots measured +2.5 % there (profiles/r05/ab_slots/).
+  static constexpr bool AB = true;
+  // reg, pred and feasible are one slot each (a.reg[0], a.pred[0], a.feasible[0]) instead of
+  // per-trajectory arrays -- the persistent solver's speculative candidates (ipm_persistent.hip:
+  // SPEC) each solve the same blocks with their own regularisation and keep those three in LDS.
+  static constexpr bool IO0 = false;
+  // (the stand-alone scan kernels) the first stage a lane runs in phase 3, where Phi = I and
+  // phi = 0 still, assigns Phi = F, phi = f instead of forming I * F and 0 + I * f
+  // (riccati_stage).  Off inside the persistent solvers: the extra copy of the stage costs
+  // their instances registers (pendulum 158 -> 168-170 VGPRs and 3 -> 2 waves per SIMD, cart-pole
+  // two-wave 352 -> 376-448 B of scratch, compiler's resource report) for 8-56 FMAs per chunk.
+  static constexpr bool PEEL = false;
+  // KEEP > 0 (the stand-alone compact scan, kkt_compact_src.h; needs PEEL, no CACHE, no AB, no
+  // affine term): the hand-off widened to the chunk's first KEEP slots.  Phase 3 keeps the compact
+  // A, B record (SRC::pack_ab: the variable entries, SRC::kRecAB doubles) of every slot j < KEEP
+  // in a register buffer, phase 4 expands them again (SRC::unpack_ab: the doubles the re-read's
+  // expand gives) and re-reads only the slots j >= KEEP, the first of them issued before the
+  // forward scan, which it does not depend on.  Phase 3's loop then runs over the wave-uniform
+  // slot (lanes with the shorter chunk sit out its first pass instead of its last), so the buffer
+  // is indexed by a scalar and stays in registers.  Off (0) everywhere else: the one-stage
+  // hand-off above.
+  static constexpr int KEEP = 0;
+  // (the stand-alone scan kernels) the non-masked scan levels of phases 2 and 4 fetch their
+  // partners with the identity select folded into the DPP instruction (combine_sklansky,
+  // sklansky_fwd_level): the same bits in half the fetch instructions.  On for nx <= 4 (the 256-
+  // register nx = 4 instances; nx <= 2 and the 512-register instances are masked and have no
+  // select to fold); the nx = 8 instances, whose elements live in scratch, and the persistent
+  // solvers compile exactly what they compiled without it.
+  static constexpr bool FOLD = false;
+};
+template <bool IO0_>  // the defaults but IO0 (the persistent solver, ipm_solve_body.h)
+struct ScanOptIO0 : ScanOpt { static constexpr bool IO0 = IO0_; };
+// whether an instance keeps A, B slots in LDS: the one rule (ScanOpt::AB)
+template <class OPT, int NX, int NU>
+constexpr bool scan_ab() { return OPT::AB && OPT::BIG && ab_supported<NX, NU>(); }
+
 // The whole KKT solve of trajectory `traj` by lane `l` of its L-lane segment (the kernel below;
 // also called by the persistent interior-point solver, ipm_persistent.hip).  With lds_out set and
 // dx = du = NULL the step stays in the LDS slots (x_s at slot s, u_s after it, x_N at slot N).
-// CACHE > 0 (caller guarantees every chunk has <= CACHE stages): the lane's chunk is loaded into
-// registers once, all loads issued up front, and phases 1, 3 and 4 read it from there -- one pass
-// over the blocks and one exposed memory latency instead of three dependent load chains (small
-// nx with one- or two-stage chunks, c2).
-// HANDOFF: phase 3 hands the chunk's first stage (A, B) to phase 4 in registers (standalone
-// scan: −1 stage of phase 4's re-reads); also inside the persistent solver since round 5, whose
-// solve is bound by its workspace traffic (profiles/r05/handoff_persist/).
-// BIG: the instance owns a SIMD (512 registers): the combines run masked (no identity partner).
-// AB (default: the 512-register L = 32 / 64 instances, BIG, where one wave per SIMD leaves 40 KB of
-// LDS per wave): A, B of chunk slots j < a.ab_slots stay in LDS from phase 1 to phases 3 and 4
-// (lds_ab); a.ab_slots = 0 turns it off at run time.  Not in the two-wave segments (L = 128): their
-// re-reads are L2 hits already, and the slots measured +2.5 % there (profiles/r05/ab_slots/).
-// IO0: reg, pred and feasible are one slot each (a.reg[0], a.pred[0], a.feasible[0]) instead of
-// per-trajectory arrays -- the persistent solver's speculative candidates (ipm_persistent.hip: SPEC)
-// each solve the same blocks with their own regularisation and keep those three in LDS.
-// PEEL (the stand-alone scan kernels): the first stage a lane runs in phase 3, where Phi = I and
-// phi = 0 still, assigns Phi = F, phi = f instead of forming I * F and 0 + I * f (riccati_stage).
-// Off inside the persistent solvers: the extra copy of the stage costs their instances registers
-// (pendulum 158 -> 168-170 VGPRs and 3 -> 2 waves per SIMD, cart-pole two-wave 352 -> 376-448 B of
-// scratch, compiler's resource report) for 8-56 FMAs per chunk.
-// KEEP > 0 (the stand-alone compact scan, kkt_compact_src.h; needs PEEL, no CACHE, no AB, no affine
-// term): the hand-off widened to the chunk's first KEEP slots.  Phase 3 keeps the compact A, B
-// record (SRC::pack_ab: the variable entries, SRC::kRecAB doubles) of every slot j < KEEP in a
-// register buffer, phase 4 expands them again (SRC::unpack_ab: the doubles the re-read's expand
-// gives) and re-reads only the slots j >= KEEP, the first of them issued before the forward scan,
-// which it does not depend on.  Phase 3's loop then runs over the wave-uniform slot (lanes with the
-// shorter chunk sit out its first pass instead of its last), so the buffer is indexed by a scalar
-// and stays in registers.  Off (0) everywhere else: the one-stage hand-off above.
-// FOLD (the stand-alone scan kernels): the non-masked scan levels of phases 2 and 4 fetch their
-// partners with the identity select folded into the DPP instruction (combine_sklansky,
-// sklansky_fwd_level): the same bits in half the fetch instructions.  On for nx <= 4 (the 256-
-// register nx = 4 instances; nx <= 2 and the 512-register instances are masked and have no select
-// to fold); the nx = 8 instances, whose elements live in scratch, and the persistent solvers
-// compile exactly what they compiled without it.
-template <int NX, int NU, int L, bool AFF, bool TILED, class SRC, int CACHE = 0, bool HANDOFF = true,
-          bool BIG = false, bool NT3 = false, bool AB = (BIG && ab_supported<NX, NU>()), bool IO0 = false,
-          bool PEEL = false, int KEEP = 0, bool FOLD = false>
+// OPT: a ScanOpt.  (Inside a generic lambda name OPT::X, not the local constant X below: the
+// lambda would capture the local, and the kernels then compile to other instructions.)
+template <int NX, int NU, int L, bool AFF, bool TILED, class SRC, class OPT = ScanOpt>
 NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, const SRC& src) {
+  constexpr int CACHE = OPT::CACHE, KEEP = OPT::KEEP;
+  constexpr bool HANDOFF = OPT::HANDOFF, BIG = OPT::BIG, NT3 = OPT::NT3, AB = scan_ab<OPT, NX, NU>(),
+                 IO0 = OPT::IO0, PEEL = OPT::PEEL, FOLD = OPT::FOLD;
   constexpr int KD = kd_width<NX, NU>();
   using ST = typename SRC::Struct;  // structural zeros of A, B (DenseBlocks: none)
   static_assert(KEEP == 0 || (PEEL && HANDOFF && CACHE == 0 && !AB && !AFF && L <= 64),
@@ -702,12 +724,9 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   constexpr int LW = L > 64 ? 64 : L;
   constexpr int W = L / LW;
   static_assert(W == 1 || W == 2, "segments of up to two waves");
-  const int wv = l / LW, lw = l % LW;
-  double* join = nullptr;
+  [[maybe_unused]] const int wv = l / LW, lw = l % LW;
+  [[maybe_unused]] double* join = nullptr;
   if constexpr (W > 1) join = lds_join<NX, NU>(N, a.lds_out != 0);
-  (void)wv;
-  (void)lw;
-  (void)join;
   lds_double* lab = nullptr;
   int abn = 0;  // chunk slots whose A, B are parked in LDS
   if constexpr (AB) {
@@ -722,7 +741,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   if constexpr (CACHE > 0) {
     if (a.mode != MODE_FWD) {
       NOC_UNROLL for (int jj = 0; jj < CACHE; ++jj)
-        if (jj < len) src.stage(start + jj, jj, reg, cache[jj]);
+        if (jj < len) src.stage(start + jj, jj, cache[jj]);
     }
   }
 
@@ -739,8 +758,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   // promoted to registers; a slot is read only where phase 3 wrote it (j < len).  The store is a
   // macro, not a lambda: a lambda's body is optimised on its own first, where kbuf is a pointer,
   // and its chain of compares is folded into one store to kbuf[j] -- scratch memory.
-  double kbuf[KEEP > 0 ? KEEP : 1][REC];
-  (void)kbuf;
+  [[maybe_unused]] double kbuf[KEEP > 0 ? KEEP : 1][REC];
 #define NOC_KEEP_PUT(J, STAGE)                                                        \
   do {                                                                                \
     double rec_[REC];                                                                 \
@@ -775,7 +793,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     } else {
       for (int s = start + len - 1; s >= start; --s) {
         StageData<NX, NU> st;
-        src.stage(s, s - start, reg, st);
+        src.stage(s, s - start, st);
         if constexpr (AB) { if (s - start < abn) ab_store<NX, NU>(lab, s - start, st.A, st.B); }
         prepend<NX, NU, AFF, ST>(e, st, reg);
       }
@@ -841,8 +859,8 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     // phase 3's re-read of a stage: the last use of Q, R, M, r, q -- non-temporal in the NT3
     // instances (the launcher's cache policy, kkt_nt3)
     auto stage3 = [&](int s, StageData<NX, NU>& st) {
-      if constexpr (NT3) src_re.stage_last(s, s - start, reg, st);
-      else src_re.stage(s, s - start, reg, st);
+      if constexpr (NT3) src_re.stage_last(s, s - start, st);
+      else src_re.stage(s, s - start, st);
     };
     // first: the lane's first executed stage (s = start + len - 1), where Phi = I, phi = 0 still --
     // std::true_type / std::false_type where the call site knows it, a bool where it does not
@@ -939,7 +957,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         NOC_UNROLL for (int u = 0; u < NU; ++u) if (ST::nzB(i, u)) t += st.B(i, u) * Kk[NU * NX + u];
         f[i] = t;
       }
-      if (PEEL && first) {
+      if (OPT::PEEL && first) {
         // Phi = I, phi = 0: the products below would be I * F and 0 + I * f, sums that start at
         // 0.0 and add exact zeros around the one term 1 * x -- the same doubles as F and f for
         // finite entries, except that an entry of F or f that is -0.0 comes out of the sums as
@@ -987,7 +1005,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
           }
           for (int s = start + jl - 1; s >= start; --s) {
             StageData<NX, NU> st;
-            src_re.template stage_part<3, NT3>(s, s - start, reg, st);
+            src_re.template stage_part<3, NT3>(s, s - start, st);
             ab_load<NX, NU>(lab, s - start, st.A, st.B);
             riccati_stage(s, st, s == sfirst);
           }
@@ -1125,7 +1143,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   Mat<NX, NU> pB;
   Vec<NX> pc;
   // chunk slots phase 4 takes from kbuf (wave-uniform; the condition `handed` was set under)
-  const int kept = (KEEP > 0 && a.mode == MODE_FULL && !(a.ablate & 32)) ? KEEP : 0;
+  [[maybe_unused]] const int kept = (KEEP > 0 && a.mode == MODE_FULL && !(a.ablate & 32)) ? KEEP : 0;
   bool pre = false;
   if constexpr (KEEP > 0) {
     if (len > kept) {
@@ -1133,7 +1151,6 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
       pre = true;
     }
   }
-  (void)kept;
   affine_prefix_sklansky<NX, LW, FOLD>(Phi, phi);  // partners on the VALU (small_linalg.h)
   Vec<NX> x;
   wave_shift_up1<NX>(phi.v, x.v);  // lane l-1's prefix; segment starts: x0 / the join below
@@ -1171,13 +1188,20 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
   Mat<NX, NU> nB;
   double nK[NU * (NX + 1)];
   Vec<NX> nc;
+  // Stage S's gains K, d into KK: from the stage's LDS slot, where phase 3 left them, or from the
+  // workspace.  A macro for NOC_KEEP_PUT's reason: a lambda is optimised on its own first, and the
+  // phase then compiles to other instructions than with the fetch written out.
+#define NOC_GAINS(S, KK)                                                              \
+  do {                                                                                \
+    if (kd_lds) {                                                                     \
+      NOC_UNROLL for (int i_ = 0; i_ < NU * (NX + 1); ++i_) (KK)[i_] = slot[(S) * KD + i_]; \
+    } else {                                                                          \
+      load_Kd<NX, NU, L, TILED>(a, traj, tN + (S), (S) - start, l, cmax, (KK));       \
+    }                                                                                 \
+  } while (0)
   auto fetch = [&](int s) {
     src_re.ab(s, s - start, nA, nB, nc);
-    if (kd_lds) {
-      NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) nK[i] = slot[s * KD + i];
-    } else {
-      load_Kd<NX, NU, L, TILED>(a, traj, tN + s, s - start, l, cmax, nK);
-    }
+    NOC_GAINS(s, nK);
   };
   auto fwd_stage = [&](const int s, const Mat<NX, NX>& A, const Mat<NX, NU>& Bm, const Vec<NX>& cc,
                        const double* Kk) {
@@ -1211,11 +1235,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         if (jj < len) {
           const int s = start + jj;
           double Kk[NU * (NX + 1)];
-          if (kd_lds) {
-            NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) Kk[i] = slot[s * KD + i];
-          } else {
-            load_Kd<NX, NU, L, TILED>(a, traj, tN + s, jj, l, cmax, Kk);
-          }
+          NOC_GAINS(s, Kk);
           Vec<NX> cc;
           if constexpr (AFF) cc = cache[jj].c; else set_zero(cc);
           fwd_stage(s, cache[jj].A, cache[jj].B, cc, Kk);
@@ -1236,11 +1256,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
           set_zero(cc);
           if constexpr (AFF) { if (a.c) src_re.cvec(s, s - start, cc); }
           double Kk[NU * (NX + 1)];
-          if (kd_lds) {
-            NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) Kk[i] = slot[s * KD + i];
-          } else {
-            load_Kd<NX, NU, L, TILED>(a, traj, tN + s, s - start, l, cmax, Kk);
-          }
+          NOC_GAINS(s, Kk);
           fwd_stage(s, A, Bm, cc, Kk);
         }
         s0 = start + jl;
@@ -1260,11 +1276,7 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
             static_for<REC>([&](auto IC) { rec[decltype(IC)::value] = kbuf[k][decltype(IC)::value]; });
             src.unpack_ab(rec, A, Bm, cc);
             double Kk[NU * (NX + 1)];
-            if (kd_lds) {
-              NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) Kk[i] = slot[s * KD + i];
-            } else {
-              load_Kd<NX, NU, L, TILED>(a, traj, tN + s, k, l, cmax, Kk);
-            }
+            NOC_GAINS(s, Kk);
             fwd_stage(s, A, Bm, cc, Kk);
           }
         });
@@ -1278,20 +1290,12 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
         nA = pA;
         nB = pB;
         nc = pc;
-        if (kd_lds) {
-          NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) nK[i] = slot[s0 * KD + i];
-        } else {
-          load_Kd<NX, NU, L, TILED>(a, traj, tN + s0, s0 - start, l, cmax, nK);
-        }
+        NOC_GAINS(s0, nK);
       } else if (handed && s0 == start) {  // stage `start` from phase 3's registers; only its K, d from LDS
         nA = hA;
         nB = hB;
         nc = hc;
-        if (kd_lds) {
-          NOC_UNROLL for (int i = 0; i < NU * (NX + 1); ++i) nK[i] = slot[start * KD + i];
-        } else {
-          load_Kd<NX, NU, L, TILED>(a, traj, tN + start, 0, l, cmax, nK);
-        }
+        NOC_GAINS(start, nK);
       } else {
         fetch(s0);
       }
@@ -1345,16 +1349,40 @@ NOC_DEV void kkt_scan_wave_src(const KKTArgs& a, const int traj, const int l, co
     }
   }
   NOC_STAMP(6);
+#undef NOC_GAINS
 #undef NOC_KEEP_PUT
 }
 
-template <int NX, int NU, int L, bool AFF, bool TILED, int CACHE = 0, bool HANDOFF = true,
-          bool BIG = false, bool NT3 = false>
+template <int NX, int NU, int L, bool AFF, bool TILED, class OPT>
 NOC_DEV void kkt_scan_wave(const KKTArgs& a, const int traj, const int l) {
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
   const ArgsSrc<NX, NU, L, AFF, TILED> src{a, traj, l, cmax, (size_t)traj * a.N};
-  kkt_scan_wave_src<NX, NU, L, AFF, TILED, ArgsSrc<NX, NU, L, AFF, TILED>, CACHE, HANDOFF, BIG, NT3,
-                    (BIG && ab_supported<NX, NU>()), false, true, 0, (NX <= 4)>(a, traj, l, src);  // PEEL, no KEEP, FOLD
+  kkt_scan_wave_src<NX, NU, L, AFF, TILED, ArgsSrc<NX, NU, L, AFF, TILED>, OPT>(a, traj, l, src);
+}
+
+// kkt_scan_kernel's options (the non-temporal phase 3 only where phase 3 re-reads tiled blocks)
+template <int NX, bool TILED, int CACHE_, bool BIG_, bool NT3_>
+struct ScanKernelOpt : ScanOpt {
+  static constexpr int CACHE = CACHE_;
+  static constexpr bool BIG = BIG_, NT3 = NT3_ && TILED && CACHE_ == 0, PEEL = true, FOLD = NX <= 4;
+};
+
+// A wave of a stand-alone scan kernel (one-wave segments) with no trajectory to solve (past the
+// batch, or masked off) still meets the one workgroup barrier its block's other waves reach at the
+// copy-out (lds_out, full / forward mode, no early-exit ablation: the same condition as the main
+// path's barrier), so every wave of the block issues that barrier exactly once.  With L < 64 one
+// wave holds several segments, and only some may be dead: then the live segments' lanes issue the
+// wave's one barrier at the copy-out and the dead lanes just leave -- the barrier here is taken
+// only by a wave with no live segment at all (a wave-uniform branch, never lane-divergent).
+// Returns whether the lane has a trajectory to solve; called at the wave's full EXEC.
+NOC_DEV bool scan_lane_live(const KKTArgs& a, const int traj) {
+  const bool dead = traj >= a.B || (a.active && a.active[traj] == 0);
+  const bool wave_live = __any(!dead);  // voted at the wave's full EXEC, before any branch
+  if (dead) {
+    if (!wave_live && a.lds_out && a.mode != MODE_BWD && !(a.ablate & 6)) __syncthreads();
+    return false;
+  }
+  return true;
 }
 
 // BIG (L = 32, 64; nx = 3, 4): one wave per SIMD -- for batches whose waves all fit one per SIMD
@@ -1373,21 +1401,9 @@ __global__ __launch_bounds__(L > 64 ? L : 256, (L > 64 || BIG) ? 1 : NOC_KKT_WAV
   if constexpr (L > 64 || BIG) asm volatile("" ::: "a255");
   const int traj = tid / L;
   if constexpr (L <= 64) {
-    // A wave with no trajectory to solve (past the batch, or masked off) still meets the one
-    // workgroup barrier its block's other waves reach at the copy-out (lds_out, full / forward
-    // mode, no early-exit ablation: the same condition as the main path's barrier), so every wave
-    // of the block issues that barrier exactly once.  With L < 64 one wave holds several
-    // segments, and only some may be dead: then the live segments' lanes issue the wave's one
-    // barrier at the copy-out and the dead lanes just leave -- the barrier here is taken only by
-    // a wave with no live segment at all (a wave-uniform branch, never lane-divergent).
-    const bool dead = traj >= a.B || (a.active && a.active[traj] == 0);
-    const bool wave_live = __any(!dead);  // voted at the wave's full EXEC, before any branch
-    if (dead) {
-      if (!wave_live && a.lds_out && a.mode != MODE_BWD && !(a.ablate & 6)) __syncthreads();
-      return;
-    }
+    if (!scan_lane_live(a, traj)) return;
   }
-  kkt_scan_wave<NX, NU, L, AFF, TILED, CACHE, true, BIG, NT3 && TILED && CACHE == 0>(a, traj, tid % L);
+  kkt_scan_wave<NX, NU, L, AFF, TILED, ScanKernelOpt<NX, TILED, CACHE, BIG, NT3>>(a, traj, tid % L);
 }
 
 // Register-cached chunk length for (NX, NU, L): only where a short chunk's blocks fit beside the
@@ -1397,11 +1413,19 @@ constexpr int kkt_cache_len() { return (NX <= 2 && L >= 32) ? 2 : 0; }
 
 
 // ---------------------------------------------------------------------------------------------
-// (not static: a shape whose instances take long to compile splits its lane counts over units,
-// kkt_scan_8x4*.hip, by explicit instantiation)
-template <int NX, int NU, int L, bool AFF>
-hipError_t launch_kkt(const KKTArgs& a_in, hipStream_t stream) {
-  KKTArgs a = a_in;
+// Launch geometry of the stand-alone scan kernels (launch_kkt below; launch_kkt_compact,
+// kkt_compact_src.h): which instance, its workgroups and their LDS.
+struct KKTLaunch {
+  bool cached, big;  // the register-cached / the one-wave-per-SIMD instance (neither: the streamed one)
+  size_t lds;        // dynamic LDS bytes per workgroup
+  int block;
+  unsigned grid;
+  bool ok;           // K, d are there where they are the workspace (no LDS slots)
+};
+// Also sets a.lds_out, a.ab_slots and a.lds_base.  AB_SLOTS: the kernel has the A, B slots
+// (ScanOpt::AB; the compact kernel has not).
+template <int NX, int NU, int L, bool AB_SLOTS>
+KKTLaunch kkt_launch_geometry(KKTArgs& a) {
   const long long threads = (long long)a.B * L;
   constexpr int CC = kkt_cache_len<NX, NU, L>();
   const int cmax = a.N / L + (a.N % L ? 1 : 0);
@@ -1420,7 +1444,7 @@ hipError_t launch_kkt(const KKTArgs& a_in, hipStream_t stream) {
   // The 512-register instances (BIG) have 40 KB of LDS per wave (160 KB per CU at one wave per
   // SIMD) against the slots' <= 20 KB: behind the slots they keep A, B of as many chunk slots as
   // fit (AB), one wave per workgroup
-  if (big) {
+  if (AB_SLOTS && big) {
     const size_t per_traj = (size_t)(((long long)a.N * kd_width<NX, NU>() + NX + 1) & ~1LL);
     const size_t segs = 64 / L;
     const size_t base = slots1 > 0 ? segs * per_traj : 0;
@@ -1443,7 +1467,17 @@ hipError_t launch_kkt(const KKTArgs& a_in, hipStream_t stream) {
   }
   const int block = L > 64 ? L : 64 * wpb;
   const unsigned grid = (unsigned)((threads + block - 1) / block);
-  if (!a.lds_out && (!a.K || !a.d)) return hipErrorInvalidValue;  // K/d needed as workspace
+  return {cached, big, lds, block, grid, a.lds_out || (a.K && a.d)};
+}
+
+// (not static: a shape whose instances take long to compile splits its lane counts over units,
+// kkt_scan_8x4*.hip, by explicit instantiation)
+template <int NX, int NU, int L, bool AFF>
+hipError_t launch_kkt(const KKTArgs& a_in, hipStream_t stream) {
+  KKTArgs a = a_in;
+  constexpr int CC = kkt_cache_len<NX, NU, L>();
+  const auto [cached, big, lds, block, grid, ok] = kkt_launch_geometry<NX, NU, L, true>(a);
+  if (!ok) return hipErrorInvalidValue;  // K/d needed as workspace
   if (cached) {
     if (a.tiled)
       hipLaunchKernelGGL((kkt_scan_kernel<NX, NU, L, AFF, true, CC>), dim3(grid), dim3(block), lds, stream, a);

@@ -141,7 +141,6 @@ static int kkt_common(int mode, int tiled, int nx, int nu, int N, int B, int lan
   int rc = check_dims(nx, nu, N, B, lanes);
   if (rc) return rc;
   const bool bwd = mode != noc::MODE_FWD;
-  const bool fwd = mode != noc::MODE_BWD;
   if ((rc = check_ptr(A, "A", true))) return rc;
   if ((rc = check_ptr(Bm, "B", true))) return rc;
   if ((rc = check_ptr(Q, "Q", bwd))) return rc;
@@ -179,8 +178,6 @@ static int kkt_common(int mode, int tiled, int nx, int nu, int N, int B, int lan
     return fail(-1, "the grouped (lanes = 1) tiled layout is supported for (nx, nu) = (8, 4)");
   if (lanes == 1 && !(64 % nx == 0 && nu <= nx))
     return fail(-1, "the group solve (lanes = 1) needs nx dividing 64 and nu <= nx");
-  (void)bwd;
-  (void)fwd;
   const int L = lanes ? lanes : noc::kkt_default_lanes(nx, nu, N);
   const bool on_chip = mode == noc::MODE_FULL && (dx || du) && noc::kkt_lds_bytes_rt(nx, nu, N, L) > 0;
   if ((!K || !d) && !on_chip)
