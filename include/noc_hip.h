@@ -298,6 +298,36 @@ int noc_debug_phase_cycles(long long* out, int n, int reset);
 int noc_debug_traj_times(long long* out, int n);
 int noc_ipm_solve(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, double bp0,
                   int max_solves, void* stream);
+/* What noc_ipm_solve (with_params != 0: noc_ipm_solve_params) would launch for a workspace of Bt
+ * trajectories, horizon N, lanes 64, these flags and an order (ordered != 0) or none, with the
+ * environment switches as they are now (csrc/ipm_plan.h: PersistKnobs, the single list) -- for
+ * tests, tools and the Python host's schedule.  (Added after NOC_ABI_VERSION 5: detected by
+ * symbol.)  simds: SIMDs of the device to plan for (4 per CU; MI355X: 1024), 0 = the current
+ * device's; with simds != 0 no device is touched.  Writes out[NOC_PLAN_*], n >= NOC_PLAN_INTS:
+ *   FAMILY      0: no persistent solve of this (family, N); 1: the one-wave kernel; 2: the wide one
+ *   WIDE_WAVES, WIDE_LDS   the wide kernel's waves per trajectory and LDS bytes per workgroup
+ *   HEAVY       > 0: the heavy-first split -- the launch at MAIN solves the first HEAVY entries of
+ *               the order, concurrently with the launch at REST on the others; 0: MAIN is the launch
+ *   MAIN + i, REST + i   a one-wave-kernel launch: WPS (waves per SIMD of its register budget), SPEC
+ *               (waves = speculative candidates per trajectory), RESUME, XLDS (x, u in LDS), STRUCT
+ *               (structure-aware blocks; 0: dense), GRID (workgroups of 64 * SPEC threads), LDS (bytes)
+ * Fields that do not apply are 0.  Returns 0, or < 0 on an argument error. */
+#define NOC_PLAN_FAMILY 0
+#define NOC_PLAN_WIDE_WAVES 1
+#define NOC_PLAN_WIDE_LDS 2
+#define NOC_PLAN_HEAVY 3
+#define NOC_PLAN_MAIN 4
+#define NOC_PLAN_REST 11
+#define NOC_PLAN_WPS 0
+#define NOC_PLAN_SPEC 1
+#define NOC_PLAN_RESUME 2
+#define NOC_PLAN_XLDS 3
+#define NOC_PLAN_STRUCT 4
+#define NOC_PLAN_GRID 5
+#define NOC_PLAN_LDS 6
+#define NOC_PLAN_INTS 18
+int noc_debug_ipm_plan(const noc_family* fam, int N, int Bt, int flags, int ordered,
+                       int with_params, int simds, int* out, int n);
 
 /* ---- per-trajectory cost parameters ------------------------------------------------------------
  * (Entry points added after NOC_ABI_VERSION 5; the version and the structs above are unchanged, so

@@ -22,6 +22,7 @@
 #include "../../include/noc_hip.h"
 #include "block_struct.h"
 #include "ipm_family.h"
+#include "ipm_plan.h"
 #include "ipm_schedule.h"
 #include "kkt_compact_src.h"
 #include "kkt_scan_impl.h"
@@ -55,13 +56,11 @@ struct SpecIO {
   int feasible, pad2[3];
 };
 
-// LDS of one workgroup, in doubles: SPEC regions of KKT slots (lds_slots: one per 64-lane
-// segment), SPEC parked states, SPEC SpecIO records (SPEC > 1 only), then SPEC copies of x, u
-// (XLDS).  SPEC = 1 is the one-wave layout: [slots][state][x, u].
+// LDS of one workgroup: the layout and its sizes are ipm_plan.h's (the launch is sized by the same
+// functions); here with the kernels' template constants.
+static_assert(sizeof(IpmState) == kIpmStateBytes && sizeof(SpecIO) == kSpecIOBytes, "ipm_plan.h sizes the LDS");
 template <int NX, int NU>
-__host__ __device__ constexpr int slot_doubles(int N) { return (N * kd_width<NX, NU>() + NX + 1) & ~1; }
-__host__ __device__ constexpr int state_doubles() { return (int)((sizeof(IpmState) + 15) / 16) * 2; }
-__host__ __device__ constexpr int specio_doubles(int spec) { return spec > 1 ? (int)(sizeof(SpecIO) / 8) * spec : 0; }
+__host__ __device__ constexpr int slot_doubles(int N) { return noc::slot_doubles(NX, NU, N); }
 template <int NX, int NU>
 NOC_DEV IpmState* state_slot(int N, int spec = 1, int wv = 0) {
   extern __shared__ __attribute__((aligned(16))) double noc_smem[];
@@ -78,11 +77,7 @@ NOC_DEV SpecIO* spec_io(int N, int spec, int wv) {
 // them; from the workspace each access was a global round trip), copied in at the start and out
 // at the end.  Layout behind the KKT slots and the parked state: x [(N+1) NX], u [N NU].
 template <int NX, int NU>
-__host__ __device__ constexpr int xlds_doubles(int N) { return ((N + 1) * NX + N * NU + 1) & ~1; }
-template <int NX, int NU>
-__host__ __device__ constexpr int xlds_off(int N, int spec = 1, int wv = 0) {
-  return spec * (slot_doubles<NX, NU>(N) + state_doubles()) + specio_doubles(spec) + wv * xlds_doubles<NX, NU>(N);
-}
+__host__ __device__ constexpr int xlds_off(int N, int spec = 1, int wv = 0) { return noc::xlds_off(NX, NU, N, spec, wv); }
 
 }  // namespace
 
@@ -139,168 +134,66 @@ __global__ __launch_bounds__(64, WPS) void ipm_solve_params_kernel(noc_family pr
 #include "ipm_solve_body.h"
 }
 
-// LDS of one persistent workgroup: the trajectory's KKT slots + the parked state.  Up to 64 KB
-// (long horizons at small batch, e.g. the reference's N = 1000 timing runs: 2 workgroups per CU).
-static size_t solve_lds_bytes(int nx, int nu, int N) {
-  const size_t slots = (size_t)(((long long)N * nu * (nx + 1) + nx + 1) & ~1LL) * sizeof(double);
-  const size_t bytes = slots + sizeof(IpmState) + 16;
-  return bytes <= 65536 ? bytes : 0;
+// Constant dispatch, as for_family: fn(std::integral_constant<int, V>) for the V of Vs... equal to
+// v -- a run-time value of the plan as a template argument of the instance -- and its result;
+// `none` if v is none of them.
+template <int... Vs, class R, class Fn>
+inline R for_const(int v, R none, Fn&& fn) {
+  R r = none;
+  (void)((v == Vs && ((void)(r = fn(std::integral_constant<int, Vs>{})), true)) || ...);
+  return r;
 }
 
-// SIMDs of the current device (4 per CU); 0 if the query fails
-static int device_simds() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return 4 * cus;
-}
+struct SolveArgs {
+  const noc_family& p;
+  const double* tp;  // per-trajectory records (noc_ipm_solve_params) or NULL
+  int mode, terminal;
+  double bp0;
+  int max_solves;
+};
 
-// Families whose kernel spills at 2 waves per SIMD (cart-pole) get a second instance at 1 wave per
-// SIMD (512 registers per lane: no scratch, stage pairs), used when the batch fits one wave per
-// SIMD anyway (B <= 4 x CUs: the reference's B = 1 runs, c2-sized batches); larger batches keep 2
-// waves per SIMD for latency hiding.  The others stay at 2 waves (their 1-wave instance measured
-// 5-7 % slower at B = 1).  NOC_PERSIST_WAVES=1|2 overrides the choice (timing experiments).
-template <int KIND>
-constexpr bool one_wave_instance() { return KIND == NOC_FAMILY_CARTPOLE; }
-
-// grid: workgroups = the entries of w.order this launch solves (w.Bt without an order)
-template <int KIND, int NX, int NU, int WPS, bool RESUME, bool XLDS>
-static hipError_t launch_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                               double bp0, int max_solves, size_t lds, hipStream_t s, int grid,
-                               const double* tp = nullptr) {
-  if (tp) {  // per-trajectory parameters: the structure-aware instance only
-    hipLaunchKernelGGL((ipm_solve_params_kernel<KIND, NX, NU, WPS, RESUME, XLDS>), dim3(grid), dim3(64), lds, s,
-                       p, w, tp, mode, terminal, bp0, max_solves);
-    return hipGetLastError();
-  }
-  // the structure-aware blocks unless NOC_PERSIST_STRUCT=0 (per launch: tests switch it)
-  const char* senv = getenv("NOC_PERSIST_STRUCT");
-  if (senv && atoi(senv) == 0)
-    hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, WPS, RESUME, XLDS, false>), dim3(grid), dim3(64),
-                       lds, s, p, w, mode, terminal, bp0, max_solves);
-  else
-    hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, WPS, RESUME, XLDS, true>), dim3(grid), dim3(64),
-                       lds, s, p, w, mode, terminal, bp0, max_solves);
-  return hipGetLastError();
-}
-
-// Speculative retries (SPEC waves per trajectory, the one-wave-per-SIMD register budget): when
-// the batch leaves SIMDs idle, a trajectory's workgroup runs SPEC waves on SPEC SIMDs, wave k
-// solving the KKT system and the trial of the k-th candidate of the regularisation's failure chain
-// (rp, rp r_inc, rp r_inc 2 r_inc, ...; P:167-173) at the same point; the accept tests are then
-// replayed in solve order (ipm_solve_kernel), so counters and iterates are the one-wave solver's
-// bit for bit.  A rejected trial no longer costs a KKT solve on the trajectory's serial chain:
-// the heaviest of 512 cart-poles, 492 computed solves, takes 345 rounds at two candidates, 266 at
-// four (tools/spec_estimate.py).  Needs x, u in LDS per wave.
-// NOC_PERSIST_SPEC=1|2|4 overrides the choice.
-static size_t spec_lds_rt(int nx, int nu, int N, int spec) {  // = xlds_off(N, spec, 0) + spec x, u
-  const long long slots = ((long long)N * nu * (nx + 1) + nx + 1) & ~1LL;
-  const long long xu = ((long long)(N + 1) * nx + (long long)N * nu + 1) & ~1LL;
-  return (size_t)(spec * (slots + state_doubles() + xu) + specio_doubles(spec)) * sizeof(double);
-}
+// One launch of the plan: the instance its fields name.  The instances that exist: SPEC > 1 only
+// at WPS = 1 with XLDS and STRUCT, the per-trajectory twin only at STRUCT and SPEC = 1, WPS = 1
+// only for the families with a one-wave instance.  (The value lists are in the order that keeps
+// the unit's kernels where they were in its device code.)
 template <int KIND, int NX, int NU>
-static size_t spec_lds_bytes(int N, int spec) {
-  return (size_t)(xlds_off<NX, NU>(N, spec, 0) + spec * xlds_doubles<NX, NU>(N)) * sizeof(double);
-}
-// Candidates per trajectory for this launch: 4 when four waves per trajectory still leave a SIMD
-// each (B <= #SIMDs / 4), else 2 (B <= #SIMDs / 2), else 1; 1 for an ordered launch (its grid is
-// the whole batch, most of it done), and when x, u of every wave do not fit 40 KB of LDS per wave.
-// A resume may run them (the tail of a large batch, gathered: BatchedIPM.solve_persistent).  The
-// families with a one-wave instance only (cart-pole).  NOC_PERSIST_SPEC=1|2|4 forces it.
-static int spec_auto(const noc_family& p, const noc_ipm_ws& w, int simds, bool launch_state) {
-  if (p.kind != NOC_FAMILY_CARTPOLE) return 1;
-  if (launch_state && w.order) return 1;
-  const char* senv = getenv("NOC_PERSIST_STRUCT");
-  if (senv && atoi(senv) == 0) return 1;
-  const char* env = getenv("NOC_PERSIST_SPEC");  // per launch (A/B sweeps in one process)
-  int want;
-  if (env) {
-    want = atoi(env);
-  } else if (simds <= 0) {
-    want = 1;
-  } else {
-    want = (long long)w.Bt * 4 <= simds ? 4 : ((long long)w.Bt * 2 <= simds ? 2 : 1);
-  }
-  if (want != 2 && want != 4) return 1;
-  return spec_lds_rt(p.nx, p.nu, w.N, want) <= (size_t)want * 40960u ? want : 1;
-}
-// grid: workgroups = the entries of w.order this launch solves (w.Bt without an order)
-template <int KIND, int NX, int NU, int SPEC>
-static hipError_t launch_spec(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                              double bp0, int max_solves, hipStream_t s, int grid = -1) {
-  if (grid < 0) grid = w.Bt;
-  const size_t lds = spec_lds_bytes<KIND, NX, NU>(w.N, SPEC);
-  if (w.flags & NOC_WS_RESUME)
-    hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, 1, true, true, true, SPEC>), dim3(grid), dim3(64 * SPEC),
-                       lds, s, p, w, mode, terminal, bp0, max_solves);
-  else
-    hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, 1, false, true, true, SPEC>), dim3(grid), dim3(64 * SPEC),
-                       lds, s, p, w, mode, terminal, bp0, max_solves);
-  return hipGetLastError();
+static hipError_t launch_one(const PersistLaunch& L, const SolveArgs& a, const noc_ipm_ws& w, hipStream_t s) {
+  const hipError_t none = hipErrorInvalidValue;
+  const dim3 grid(L.grid), block(64 * L.spec);
+  const size_t lds = (size_t)L.lds;
+  return for_const<1, 4, 2>(L.spec, none, [&](auto SPEC) {
+    return for_const<2, 1>(L.wps, none, [&](auto WPS) {
+      return for_const<0, 1>(L.xlds, none, [&](auto XLDS) {
+        return for_const<0, 1>(L.resume, none, [&](auto RES) {
+          if constexpr ((WPS == 1 && !one_wave_instance(KIND)) || (SPEC > 1 && !(WPS == 1 && XLDS))) {
+            return none;
+          } else if constexpr (SPEC > 1) {
+            if (a.tp || !L.strct) return none;
+            hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, WPS, RES, XLDS, true, SPEC>), grid, block, lds, s,
+                               a.p, w, a.mode, a.terminal, a.bp0, a.max_solves);
+            return hipGetLastError();
+          } else {
+            if (a.tp)
+              hipLaunchKernelGGL((ipm_solve_params_kernel<KIND, NX, NU, WPS, RES, XLDS>), grid, block, lds, s,
+                                 a.p, w, a.tp, a.mode, a.terminal, a.bp0, a.max_solves);
+            else if (!L.strct)
+              hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, WPS, RES, XLDS, false>), grid, block, lds, s,
+                                 a.p, w, a.mode, a.terminal, a.bp0, a.max_solves);
+            else
+              hipLaunchKernelGGL((ipm_solve_kernel<KIND, NX, NU, WPS, RES, XLDS, true>), grid, block, lds, s,
+                                 a.p, w, a.mode, a.terminal, a.bp0, a.max_solves);
+            return hipGetLastError();
+          }
+        });
+      });
+    });
+  });
 }
 
-template <int KIND, int NX, int NU, int WPS>
-static hipError_t solve_w(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                          double bp0, int max_solves, size_t lds, hipStream_t s, int grid = -1,
-                          const double* tp = nullptr) {
-  if (grid < 0) grid = w.Bt;
-  // x, u in LDS (XLDS) when that keeps the residency the register budget allows: 8 waves per CU
-  // at 2 waves per SIMD (<= 20 KB per wave), 4 at one wave per SIMD (<= 40 KB); longer horizons
-  // keep them in the workspace.  NOC_PERSIST_XLDS=0 forces the workspace (A/B).
-  const char* xenv = getenv("NOC_PERSIST_XLDS");  // per launch (tests switch it)
-  const size_t xl = lds + (size_t)(((w.N + 1) * NX + w.N * NU + 1) & ~1) * sizeof(double);
-  const bool xlds = !(xenv && atoi(xenv) == 0) && xl <= (WPS == 1 ? 40960u : 20480u);
-  const bool res = (w.flags & NOC_WS_RESUME) != 0;
-  if (xlds)
-    return res ? launch_solve<KIND, NX, NU, WPS, true, true>(p, w, mode, terminal, bp0, max_solves, xl, s, grid, tp)
-               : launch_solve<KIND, NX, NU, WPS, false, true>(p, w, mode, terminal, bp0, max_solves, xl, s, grid, tp);
-  return res ? launch_solve<KIND, NX, NU, WPS, true, false>(p, w, mode, terminal, bp0, max_solves, lds, s, grid, tp)
-             : launch_solve<KIND, NX, NU, WPS, false, false>(p, w, mode, terminal, bp0, max_solves, lds, s, grid, tp);
-}
-
-// Heavy-first split of an ordered launch larger than one wave per SIMD (cart-pole): the first
-// `heavy` entries of w.order -- the costliest trajectories (the probe-ordered resume,
-// BatchedIPM.solve_persistent) -- run on the one-wave instance, a SIMD of their own, concurrently
-// with the rest on the two-wave instance (second stream, event fork / join).  Every trajectory's
-// result is the same on either instance (tested).  NOC_PERSIST_HEAVY=<n> sets the count.
-// By default (cart-pole, N <= 320, #SIMDs < B <= 2 #SIMDs: the c3 slice of 2 GPUs) the costliest
-// #SIMDs / 8 trajectories of the probe order run two speculative candidates each beside the rest
-// on the two-wave instance: 2048 cart-poles 17.9 -> 16.3-16.8 ms (probe order alone;
-// profiles/r06/t/).  At one wave per SIMD (1024) the split made the light end of the order wait
-// for SIMDs: 11.4-11.6 ms on one batch but 16.2-18.5 ms on the c3 slices (profiles/r06/final_c4/),
-// so not there; at c3 (4096) it measured slower (profiles/r06/q/).  NOC_PERSIST_HEAVY=<n> sets
-// the count, NOC_PERSIST_HEAVY_SPEC=0|2 the candidates (0 turns the default split off).
-static int heavy_count(const noc_ipm_ws& w, int simds, bool* spec2) {
-  const char* env = getenv("NOC_PERSIST_HEAVY");  // per launch (A/B sweeps in one process)
-  const char* hs = getenv("NOC_PERSIST_HEAVY_SPEC");
-  *spec2 = false;
-  if (!w.order || simds <= 0) return 0;
-  // the candidates exist on the structure-aware blocks only (launch_spec), and both launches of a
-  // split write the same w.A ... w.M: under NOC_PERSIST_STRUCT=0 no candidates (as spec_auto), so
-  // the heavy launch takes the dense one-wave instance like the rest, or there is no split
-  const char* senv = getenv("NOC_PERSIST_STRUCT");
-  const bool dense = senv && atoi(senv) == 0;
-  int h;
-  bool sp;
-  if (env) {
-    h = atoi(env);
-    sp = hs && atoi(hs) == 2 && !dense;
-    if (w.Bt <= (sp ? simds / 2 : simds)) return 0;
-  } else {
-    if (dense || (hs && atoi(hs) == 0) || w.N > 320 || w.Bt <= simds || w.Bt > 2 * simds) return 0;
-    h = simds / 8;
-    sp = true;
-  }
-  if (h < 0) h = 0;
-  if (h > simds / 2) h = simds / 2;
-  *spec2 = sp;
-  return h < w.Bt ? h : 0;
-}
-
-template <int KIND, int NX, int NU, int REST_WPS = 2>
-static hipError_t solve_split(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                              double bp0, int max_solves, size_t lds, hipStream_t s, int heavy,
-                              bool spec2) {
+// The heavy-first split (ipm_plan.h: plan_heavy): plan.main on the first plan.heavy entries of
+// w.order, concurrently with plan.rest on the others (second stream, event fork / join).
+template <int KIND, int NX, int NU>
+static hipError_t launch_split(const PersistPlan& plan, const SolveArgs& a, const noc_ipm_ws& w, hipStream_t s) {
   thread_local hipStream_t s2 = nullptr;
   thread_local hipEvent_t fork = nullptr, join = nullptr;
   if (!s2) {
@@ -311,46 +204,13 @@ static hipError_t solve_split(const noc_family& p, const noc_ipm_ws& w, int mode
   hipError_t e;
   if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
   if ((e = hipStreamWaitEvent(s2, fork, 0)) != hipSuccess) return e;
-  // the heavy launch first, so its workgroups are placed before the two-wave ones fill the SIMDs;
-  // spec2: the heavy trajectories with two speculative candidates each
-  if (spec2 && spec_lds_bytes<KIND, NX, NU>(w.N, 2) <= 2 * 40960u)
-    e = launch_spec<KIND, NX, NU, 2>(p, w, mode, terminal, bp0, max_solves, s, heavy);
-  else
-    e = solve_w<KIND, NX, NU, 1>(p, w, mode, terminal, bp0, max_solves, lds, s, heavy);
-  if (e != hipSuccess) return e;
+  // the heavy launch first, so its workgroups are placed before the two-wave ones fill the SIMDs
+  if ((e = launch_one<KIND, NX, NU>(plan.main, a, w, s)) != hipSuccess) return e;
   noc_ipm_ws rest = w;
-  rest.order = w.order + heavy;
-  if ((e = solve_w<KIND, NX, NU, REST_WPS>(p, rest, mode, terminal, bp0, max_solves, lds, s2, w.Bt - heavy)) !=
-      hipSuccess)
-    return e;
+  rest.order = w.order + plan.heavy;
+  if ((e = launch_one<KIND, NX, NU>(plan.rest, a, rest, s2)) != hipSuccess) return e;
   if ((e = hipEventRecord(join, s2)) != hipSuccess) return e;
   return hipStreamWaitEvent(s, join, 0);
-}
-
-template <int KIND, int NX, int NU>
-static hipError_t solve_t(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                          double bp0, int max_solves, hipStream_t s) {
-  const size_t lds = solve_lds_bytes(NX, NU, w.N);
-  if (lds == 0) return hipErrorInvalidValue;  // step does not fit in LDS: use the launch driver
-  if constexpr (one_wave_instance<KIND>()) {
-    static const int simds = device_simds();
-    static const char* env = getenv("NOC_PERSIST_WAVES");
-    const bool one = env ? atoi(env) == 1 : (simds > 0 && w.Bt <= simds);
-    if (one) {
-      bool sp1 = false;
-      const int heavy1 = env ? 0 : heavy_count(w, simds, &sp1);
-      if (heavy1 > 0)
-        return solve_split<KIND, NX, NU, 1>(p, w, mode, terminal, bp0, max_solves, lds, s, heavy1, sp1);
-      const int spec = spec_auto(p, w, simds, true);
-      if (spec == 2) return launch_spec<KIND, NX, NU, 2>(p, w, mode, terminal, bp0, max_solves, s);
-      if (spec == 4) return launch_spec<KIND, NX, NU, 4>(p, w, mode, terminal, bp0, max_solves, s);
-      return solve_w<KIND, NX, NU, 1>(p, w, mode, terminal, bp0, max_solves, lds, s);
-    }
-    bool sp = false;
-    const int heavy = env ? 0 : heavy_count(w, simds, &sp);
-    if (heavy > 0) return solve_split<KIND, NX, NU>(p, w, mode, terminal, bp0, max_solves, lds, s, heavy, sp);
-  }
-  return solve_w<KIND, NX, NU, 2>(p, w, mode, terminal, bp0, max_solves, lds, s);
 }
 
 int debug_phase_cycles(long long* out, int n, int reset) {
@@ -392,76 +252,67 @@ int debug_traj_times(long long* out, int n) {
                  hipSuccess ? 0 : -1;
 }
 
-// persistent instances exist for the families with nx <= 4 (an nx = 8 scan element does not fit a
-// wave's registers next to the solver state: those run the launch-per-phase driver)
-template <int NX>
-constexpr bool persistent_instance() { return NX <= 4; }
-
 bool ipm_solve_supported(const noc_family& p, int N, int lanes) {
-  if (lanes != PL) return false;
-  return for_family(p, false, [](auto, auto X, auto) { return persistent_instance<X>(); }) &&
-         solve_lds_bytes(p.nx, p.nu, N) > 0;
+  return lanes == PL && family_supported(p) && persistent_instance(p.nx) && onewave_lds_bytes(p.nx, p.nu, N) > 0;
 }
 
-// The wide kernel (ipm_wide.hip: 4 waves and the LDS of one CU per trajectory) when the batch
-// leaves CUs idle anyway (B <= #CUs: the reference's B = 1 runs) and the horizon gives the
-// one-wave kernel more than two stages per lane: at N <= 128 the one-wave solve is faster (its
-// KKT scan needs no cross-wave join), beyond it the wide one (B = 1, per KKT solve: pendulum
-// N=200 16.5 vs 20.4 us, N=800 32 vs 57 us; cart-pole N=128 31.6 vs 25.7 us, N=200 33.0 vs
-// 35.2 us -- profiles/r02/wide/crossover.jsonl).  NOC_PERSIST_WIDE=0|1 overrides.
-// (Re-packing the last <= #CUs trajectories of a large batch onto it was measured and dropped:
-// those are Newton retries, KKT-bound, and the wide KKT solve is no faster -- DESIGN.md §3.7.)
-// Where the speculative candidates apply (cart-pole, B <= #SIMDs / 2) and the horizon gives the
-// one-wave kernel at most five stages per lane (N <= 320), they beat the wide kernel: cart-pole
-// B = 1 N = 200 / 300 5.19 / 5.92 ms against 5.88 / 6.32 ms, N = 200 B = 64 / 256 7.54 / 8.30 ms
-// against 9.53 / 10.28 ms; at N = 400 the wide kernel is ahead (6.57 vs 7.02 ms;
-// profiles/r06/n/).  The choice ignores resume and order, so a capped solve resumes on the kernel
-// family (one-wave) it started on.
-static bool use_wide(const noc_family& p, const noc_ipm_ws& w) {
-  const char* env = getenv("NOC_PERSIST_WIDE");
-  if (env && atoi(env) == 0) return false;
-  if (!ipm_wide_supported(p, w.N)) return false;
-  if (env && atoi(env) == 1) return true;
-  static const int simds = device_simds();
-  const int cus = simds / 4;
-  if (w.N <= 320 && spec_auto(p, w, simds, false) > 1) return false;
-  return cus > 0 && w.Bt <= cus && w.N > 128;
+// The plan of one solve call (ipm_plan.h) for the environment as it is now.  simds = 0: the
+// current device's (then 0 if none is visible); with_params: noc_ipm_solve_params.
+static PersistPlan ipm_plan(const noc_family& p, int N, int Bt, bool ordered, int flags, bool with_params,
+                            int simds) {
+  if (!family_supported(p) || (with_params && !traj_params_supported(p))) return PersistPlan{};
+  PersistQuery q{p.kind, p.nx, p.nu, N, Bt, ordered, flags, with_params, simds ? simds : device_simds(0), 0, 0};
+  if (!with_params && ipm_wide_supported(p, N)) {
+    q.wide_lds2 = (long long)wide_lds_bytes(p, N, 2);
+    q.wide_lds4 = (long long)wide_lds_bytes(p, N, 4);
+  }
+  return plan_persist(q, read_persist_knobs());
+}
+
+// noc_debug_ipm_plan: the plan's fields at out[NOC_PLAN_*] (include/noc_hip.h)
+void debug_ipm_plan(const noc_family& p, int N, int Bt, int flags, bool ordered, bool with_params, int simds,
+                    int* out) {
+  const PersistPlan plan = ipm_plan(p, N, Bt, ordered, flags, with_params, simds);
+  for (int i = 0; i < NOC_PLAN_INTS; ++i) out[i] = 0;
+  out[NOC_PLAN_FAMILY] = plan.family;
+  out[NOC_PLAN_WIDE_WAVES] = plan.wide_waves;
+  out[NOC_PLAN_WIDE_LDS] = (int)plan.wide_lds;
+  if (plan.family != PersistPlan::kOneWave) return;
+  out[NOC_PLAN_HEAVY] = plan.heavy;
+  const PersistLaunch* ls[2] = {&plan.main, &plan.rest};
+  for (int i = 0; i < (plan.heavy > 0 ? 2 : 1); ++i) {
+    int* o = out + (i ? NOC_PLAN_REST : NOC_PLAN_MAIN);
+    const PersistLaunch& l = *ls[i];
+    o[NOC_PLAN_WPS] = l.wps; o[NOC_PLAN_SPEC] = l.spec; o[NOC_PLAN_RESUME] = l.resume; o[NOC_PLAN_XLDS] = l.xlds;
+    o[NOC_PLAN_STRUCT] = l.strct; o[NOC_PLAN_GRID] = l.grid; o[NOC_PLAN_LDS] = (int)l.lds;
+  }
+}
+
+static hipError_t launch_plan(const PersistPlan& plan, const noc_ipm_ws& w, const SolveArgs& a, hipStream_t s) {
+  if (plan.family == PersistPlan::kWide)
+    return ipm_solve_wide(a.p, w, a.mode, a.terminal, a.bp0, a.max_solves, nullptr, nullptr, w.Bt,
+                          plan.wide_waves, s);
+  if (plan.family != PersistPlan::kOneWave) return hipErrorInvalidValue;  // use the launch driver
+  return for_family(a.p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+    if constexpr (persistent_instance(X))
+      return plan.heavy > 0 ? launch_split<K, X, U>(plan, a, w, s) : launch_one<K, X, U>(plan.main, a, w, s);
+    else
+      return hipErrorInvalidValue;
+  });
 }
 
 hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal, double bp0,
                      int max_solves, hipStream_t s) {
-  if (use_wide(p, w)) {
-    static const int cus = device_simds() / 4;
-    return ipm_solve_wide(p, w, mode, terminal, bp0, max_solves, nullptr, nullptr, w.Bt,
-                          wide_waves(p, w, cus), s);
-  }
-  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
-    if constexpr (persistent_instance<X>()) return solve_t<K, X, U>(p, w, mode, terminal, bp0, max_solves, s);
-    else return hipErrorInvalidValue;
-  });
+  const PersistPlan plan = ipm_plan(p, w.N, w.Bt, w.order != nullptr, w.flags, false, 0);
+  return launch_plan(plan, w, SolveArgs{p, nullptr, mode, terminal, bp0, max_solves}, s);
 }
 
-// Per-trajectory cost parameters (noc_ipm_solve_params): always the one-wave kernel, with the
-// register budget (one or two waves per SIMD) and the x, u placement solve_t / solve_w choose for
-// the same batch -- never the wide kernel, speculative candidates or the heavy-first split, whose
-// instances read the shared family argument.
+// Per-trajectory cost parameters (noc_ipm_solve_params): the plan never gives them the wide
+// kernel, speculative candidates or the heavy-first split (ipm_plan.h).
 hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
                             int terminal, double bp0, int max_solves, hipStream_t s) {
-  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
-    if constexpr (persistent_instance<X>() && traj_params_instance<K, X, U>()) {
-      const size_t lds = solve_lds_bytes(X, U, w.N);
-      if (lds == 0) return hipErrorInvalidValue;
-      if constexpr (one_wave_instance<K>()) {
-        static const int simds = device_simds();
-        static const char* env = getenv("NOC_PERSIST_WAVES");
-        if (env ? atoi(env) == 1 : (simds > 0 && w.Bt <= simds))
-          return solve_w<K, X, U, 1>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
-      }
-      return solve_w<K, X, U, 2>(p, w, mode, terminal, bp0, max_solves, lds, s, -1, tp);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  });
+  const PersistPlan plan = ipm_plan(p, w.N, w.Bt, w.order != nullptr, w.flags, true, 0);
+  return launch_plan(plan, w, SolveArgs{p, tp, mode, terminal, bp0, max_solves}, s);
 }
 
 }  // namespace noc

@@ -716,22 +716,12 @@ int debug_wide_cycles(long long* out, int n, int reset) {
 // LDS bytes of one W-wave workgroup of family p, 0 if the trajectory does not fit in a CU
 template <int K, int X, int U>
 static size_t wide_lds_t(int N, int W) {
+  if (N > 160 * 1024 / 8) return 0;  // not even x fits (and WideLds counts in int)
   const size_t bytes = (size_t)WideLds<X, U, BlockStruct<K, X, U, true>>(N, W).total * sizeof(double);
   return bytes <= 160 * 1024 - 1024 ? bytes : 0;
 }
 size_t wide_lds_bytes(const noc_family& p, int N, int W) {
   return for_family(p, (size_t)0, [&](auto K, auto X, auto U) { return wide_lds_t<K, X, U>(N, W); });
-}
-
-// Waves per trajectory: 4 when the batch leaves CUs idle (B <= #CUs: one workgroup per CU), 2
-// when two two-wave workgroups fit a CU (512 registers per lane: one wave per SIMD) -- B up to
-// 2 x #CUs, the 8-GPU slice of c3.  NOC_WIDE_WAVES=2|4 forces one (per launch).
-int wide_waves(const noc_family& p, const noc_ipm_ws& w, int cus) {
-  const char* env = getenv("NOC_WIDE_WAVES");
-  if (env && (atoi(env) == 2 || atoi(env) == 4)) return atoi(env);
-  if (cus > 0 && w.Bt <= cus) return 4;
-  const size_t two = wide_lds_bytes(p, w.N, 2);
-  return (two > 0 && two <= 80 * 1024 - 512) ? 2 : 4;
 }
 
 bool ipm_wide_supported(const noc_family& p, int N) {

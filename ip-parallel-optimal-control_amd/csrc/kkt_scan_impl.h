@@ -1432,7 +1432,7 @@ KKTLaunch kkt_launch_geometry(KKTArgs& a) {
   const bool cached = CC > 0 && cmax <= CC && !(a.ablate & 8);  // ablation bit 3: streamed chunks
   // the batch's waves fit one per SIMD: the 512-register instance (NOC_KKT_BIG=0 disables)
   const bool big = (L == 64 || L == 32) && NX >= 3 && NX <= 4 &&
-                   (threads + 63) / 64 <= kkt_device_simds() && kkt_big_enabled();
+                   (threads + 63) / 64 <= device_simds(1024) && kkt_big_enabled();
   // L <= 64: wpb independent waves per workgroup (no LDS sharing; each its own slot region);
   // L = 128: one trajectory per two-wave workgroup (the waves join through LDS)
   const size_t slots1 = (a.mode == MODE_BWD || (!a.dx && !a.du)) ? 0 : kkt_lds_bytes_rt(NX, NU, a.N, L);

@@ -98,7 +98,7 @@ int kkt_pick_lanes(int nx, int nu, int N, int B) {
   int L = 8;
   for (int c = 64; c >= 8; c /= 2)
     if (N >= cmin * c) { L = c; break; }
-  const long simds = kkt_device_simds();
+  const long simds = device_simds(1024);
   // (3) two waves per trajectory (L = 128, nx <= 4) only when the horizon gives every lane of
   // both waves a stage and the whole batch is resident at once: that instance runs one wave per
   // SIMD (kkt_scan_kernel), so B * 2 waves must not exceed the SIMDs
@@ -513,6 +513,17 @@ int noc_ipm_solve(const noc_family* fam, const noc_ipm_ws* ws, int mode, int ter
   if (ws->Bt == 0) return 0;
   return hip_status(noc::ipm_solve(*fam, *ws, mode, terminal, bp0, max_solves,
                                    static_cast<hipStream_t>(stream)), "ipm_solve");
+}
+
+int noc_debug_ipm_plan(const noc_family* fam, int N, int Bt, int flags, int ordered, int with_params,
+                       int simds, int* out, int n) {
+  if (!fam || !out) return fail(-2, "noc_debug_ipm_plan: family or out is NULL");
+  if (n < NOC_PLAN_INTS) return fail(-1, "noc_debug_ipm_plan: out needs NOC_PLAN_INTS entries");
+  if (N < 1 || Bt < 0 || simds < 0) return fail(-1, "noc_debug_ipm_plan: need N >= 1, Bt >= 0, simds >= 0");
+  if (flags & ~(NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP))
+    return fail(-1, "noc_debug_ipm_plan: unknown flags bits set");
+  noc::debug_ipm_plan(*fam, N, Bt, flags, ordered != 0, with_params != 0, simds, out);
+  return 0;
 }
 
 long long noc_ddp_work_doubles(int nx, int nu, int N, int Bt) {

@@ -47,19 +47,18 @@ struct KKTArgs {
 // (K_s, d_s, later overwritten by dx_s, du_s) + dx_N, one region per L-lane segment of the
 // 64-thread block (L = 128: one per 128-thread block).  Staged when the region fits in 20 KB per
 // wave (8 resident waves per CU).
-// SIMDs of the current device (4 per CU); 1024 (MI355X: 256 CUs) when no device is visible.
-inline int kkt_device_simds() {
-  static int simds = 0;
-  if (simds == 0) {
+// SIMDs of the current device (4 per CU), queried once; `fallback` when no device is visible or
+// the query fails: 1024 (MI355X: 256 CUs) for the KKT scan's policies, 0 = "unknown" for the
+// persistent solver's plan (ipm_plan.h).
+inline int device_simds(int fallback) {
+  static const int simds = [] {
     int n = 0, dev = 0, cus = 0;
-    if (hipGetDeviceCount(&n) == hipSuccess && n > 0 && hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-      simds = 4 * cus;
-    else
-      simds = 1024;
+    const bool ok = hipGetDeviceCount(&n) == hipSuccess && n > 0 && hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
     (void)hipGetLastError();
-  }
-  return simds;
+    return ok && cus > 0 ? 4 * cus : 0;
+  }();
+  return simds > 0 ? simds : fallback;
 }
 
 // Independent waves per workgroup of the L <= 64 scan (the measured A/B,
@@ -73,7 +72,7 @@ inline int kkt_waves_per_block(long waves, size_t lds_per_wave) {
     const int v = e ? std::atoi(e) : 0;
     return (v == 1 || v == 2 || v == 4) ? v : 0;
   }();
-  int w = forced ? forced : (waves <= kkt_device_simds() ? 4 : 2);
+  int w = forced ? forced : (waves <= device_simds(1024) ? 4 : 2);
   while (w > 1 && lds_per_wave * w > 65536) w /= 2;
   return w;
 }
@@ -240,6 +239,9 @@ hipError_t ipm_promote(const noc_ipm_ws& w, hipStream_t s);
 hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s);
 // persistent whole-solve kernel (ipm_persistent.hip)
 bool ipm_solve_supported(const noc_family& p, int N, int lanes);
+// what ipm_solve / ipm_solve_params would launch, as out[NOC_PLAN_*] (ipm_plan.h)
+void debug_ipm_plan(const noc_family& p, int N, int Bt, int flags, bool ordered, bool with_params, int simds,
+                    int* out);
 // interior-point DDP (ddp_persistent.hip)
 bool ddp_supported(const noc_family& p);
 long long ddp_record_doubles(int nx, int nu);
@@ -287,7 +289,6 @@ hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x,
 // wide whole-solve kernel (ipm_wide.hip): one 4-wave workgroup per trajectory, LDS-resident
 bool ipm_wide_supported(const noc_family& p, int N);
 size_t wide_lds_bytes(const noc_family& p, int N, int W);
-int wide_waves(const noc_family& p, const noc_ipm_ws& w, int cus);
 int debug_wide_cycles(long long* out, int n, int reset);
 // grid workgroups solve trajectories idx[0 .. *count) (idx == NULL: 0 .. Bt-1, count ignored)
 hipError_t ipm_solve_wide(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,

@@ -81,6 +81,19 @@ WS_STATE_FIELDS = ["bp", "rp", "rinc", "cost", "hu", "gnorm", "reg"]
 
 
 FIELD_A, FIELD_B, FIELD_Q, FIELD_R, FIELD_M = range(5)  # NOC_FIELD_* (noc_compact_width)
+# NOC_PLAN_* (noc_debug_ipm_plan): out[] indices; a launch's fields are offsets from MAIN / REST
+PLAN_FAMILY, PLAN_WIDE_WAVES, PLAN_WIDE_LDS, PLAN_HEAVY, PLAN_MAIN, PLAN_REST = 0, 1, 2, 3, 4, 11
+PLAN_INTS = 18
+PLAN_WPS, PLAN_SPEC, PLAN_RESUME, PLAN_XLDS, PLAN_STRUCT, PLAN_GRID, PLAN_LDS = range(7)
+
+
+def ipm_plan(lib, fam_c, N: int, Bt: int, flags: int = 0, ordered: bool = False,
+             with_params: bool = False, simds: int = 0):
+    """noc_debug_ipm_plan: out[PLAN_*] of what a persistent solve call would launch now."""
+    out = (_i * PLAN_INTS)()
+    check(lib.noc_debug_ipm_plan(ctypes.byref(fam_c), int(N), int(Bt), int(flags), int(ordered),
+                                 int(with_params), int(simds), out, PLAN_INTS), "noc_debug_ipm_plan", lib)
+    return list(out)
 WS_OPT_FIELDS = ["order"]  # optional pointers, NULL unless set (noc_ipm_ws.order)
 
 
@@ -114,6 +127,8 @@ SIGNATURES.update({
     "noc_debug_phase_cycles": (_i, [ctypes.POINTER(ctypes.c_longlong), _i, _i]),
     "noc_debug_traj_times": (_i, [ctypes.POINTER(ctypes.c_longlong), _i]),
     "noc_ipm_solve": (_i, [_fp, _wp, _i, _i, ctypes.c_double, _i, _dp]),
+    # what a solve call would launch (added after ABI version 5: detected by symbol)
+    "noc_debug_ipm_plan": (_i, [_fp, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), _i]),
     # per-trajectory cost parameters (added after ABI version 5: detected by symbol)
     "noc_traj_params_supported": (_i, [_fp, _i, _i]),
     "noc_ipm_solve_params": (_i, [_fp, _wp, _dp, _i, _i, ctypes.c_double, _i, _dp]),

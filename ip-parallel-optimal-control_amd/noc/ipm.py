@@ -257,8 +257,8 @@ class BatchedIPM:
             schedule = "probe" if not resume and self.Bt > self._resident_slots() else "index"
         elif auto:
             # the probe order also where the launcher splits off the costliest trajectories onto
-            # speculative candidates (cart-pole, #SIMDs < B <= 2 #SIMDs: ipm_persistent.hip
-            # heavy_count): 2048 cart-poles 20.4 -> 16.3-16.8 ms (profiles/r06/t/)
+            # speculative candidates (cart-pole, #SIMDs < B <= 2 #SIMDs: csrc/ipm_plan.h
+            # plan_heavy): 2048 cart-poles 20.4 -> 16.3-16.8 ms (profiles/r06/t/)
             probe = not resume and (self.Bt > self._resident_slots() or self._heavy_split_eligible())
             schedule = "probe" if probe and not tail else "index"
         if schedule == "probe" and not resume:
@@ -298,13 +298,13 @@ class BatchedIPM:
         return 4 * torch.cuda.get_device_properties(self.device).multi_processor_count
 
     def _heavy_split_eligible(self) -> bool:
-        if os.environ.get("NOC_PERSIST_HEAVY_SPEC") == "0" or os.environ.get("NOC_PERSIST_SPEC") == "1":
+        """The launcher would split the probe schedule's ordered resume, costliest trajectories
+        on speculative candidates (csrc/ipm_plan.h: plan_heavy; asked, not restated)."""
+        if not self.persistent or os.environ.get("NOC_PERSIST_SPEC") == "1":
             return False
-        if os.environ.get("NOC_PERSIST_STRUCT") == "0":  # no candidates on dense blocks: no split
-            return False
-        simds = self._simds()
-        return (self.persistent and self.family.kind == _lib.FAMILY_CARTPOLE and self.N <= 320
-                and simds < self.Bt <= 2 * simds)
+        plan = _lib.ipm_plan(self._lib, self.fam_c, self.N, self.Bt,
+                             flags=self.ws.flags | _lib.WS_RESUME, ordered=True, simds=self._simds())
+        return plan[_lib.PLAN_HEAVY] > 0 and plan[_lib.PLAN_MAIN + _lib.PLAN_SPEC] > 1
 
     def _tail_eligible(self) -> bool:
         if os.environ.get("NOC_PERSIST_TAIL", "1") == "0" or os.environ.get("NOC_PERSIST_SPEC") == "1":

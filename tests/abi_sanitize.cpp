@@ -90,6 +90,37 @@ int main() {
   EXPECT(noc_ipm_solve(&fam, &ws, NOC_MODE_PAR, NOC_TERMINAL_STAGE0, 0.0, 10, 0) < 0);  // bp0
   EXPECT(noc_ipm_solve(&fam, &ws, NOC_MODE_PAR, NOC_TERMINAL_STAGE0, 0.1, 0, 0) < 0);   // cap
   EXPECT(noc_ipm_solve(nullptr, &ws, NOC_MODE_PAR, NOC_TERMINAL_STAGE0, 0.1, 10, 0) < 0);
+  // noc_debug_ipm_plan at the boundary rows of its table (tests/test_ipm_plan.py), for a device of
+  // 1024 SIMDs (no device is touched): argument errors, then {N, Bt, flags, ordered, with_params}
+  // -> family, heavy, and the main launch's WPS, SPEC, XLDS, LDS bytes
+  int plan[NOC_PLAN_INTS + 1];
+  plan[NOC_PLAN_INTS] = 12345;  // a canary behind the array
+  EXPECT(noc_debug_ipm_plan(nullptr, 200, 1, 0, 0, 0, 1024, plan, NOC_PLAN_INTS) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 200, 1, 0, 0, 0, 1024, nullptr, NOC_PLAN_INTS) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 200, 1, 0, 0, 0, 1024, plan, NOC_PLAN_INTS - 1) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 0, 1, 0, 0, 0, 1024, plan, NOC_PLAN_INTS) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 200, -1, 0, 0, 0, 1024, plan, NOC_PLAN_INTS) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 200, 1, 8, 0, 0, 1024, plan, NOC_PLAN_INTS) < 0);
+  EXPECT(noc_debug_ipm_plan(&fam, 200, 1, 0, 0, 0, -4, plan, NOC_PLAN_INTS) < 0);
+  const int rows[][11] = {
+      {200, 1, 0, 0, 0, /* -> */ 1, 0, 1, 4, 1, 64704},      {200, 256, 0, 0, 0, 1, 0, 1, 4, 1, 64704},
+      {200, 257, 0, 0, 0, 1, 0, 1, 2, 1, 32352},             {200, 512, 0, 0, 0, 1, 0, 1, 2, 1, 32352},
+      {200, 513, 0, 0, 0, 1, 0, 1, 1, 1, 16144},             {200, 1024, 0, 0, 0, 1, 0, 1, 1, 1, 16144},
+      {200, 1025, 0, 0, 0, 1, 0, 2, 1, 1, 16144},            {200, 1024, NOC_WS_RESUME, 1, 0, 1, 0, 1, 1, 1, 16144},
+      {200, 1025, NOC_WS_RESUME, 1, 0, 1, 128, 1, 2, 1, 32352}, {200, 2048, NOC_WS_RESUME, 1, 0, 1, 128, 1, 2, 1, 32352},
+      {200, 2049, NOC_WS_RESUME, 1, 0, 1, 0, 2, 1, 1, 16144}, {321, 2048, NOC_WS_RESUME, 1, 0, 1, 0, 2, 1, 0, 12960},
+      {254, 1025, 0, 0, 0, 1, 0, 2, 1, 1, 20464},            {255, 1025, 0, 0, 0, 1, 0, 2, 1, 0, 10320},
+      {320, 1024, 0, 0, 0, 1, 0, 1, 1, 1, 25744},            {400, 1, 0, 0, 0, 2, 0, 0, 0, 0, 0},
+      {200, 1, 0, 0, 1, 1, 0, 1, 1, 1, 16144},               {200, 1025, 0, 0, 1, 1, 0, 2, 1, 1, 16144},
+      {200, 2048, NOC_WS_RESUME, 1, 1, 1, 0, 2, 1, 1, 16144}, {1636, 4, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+      {2147483647, 2147483647, 0, 1, 0, 0, 0, 0, 0, 0, 0}};
+  for (const auto& r : rows) {
+    EXPECT(noc_debug_ipm_plan(&fam, r[0], r[1], r[2], r[3], r[4], 1024, plan, NOC_PLAN_INTS) == 0);
+    const int* m = plan + NOC_PLAN_MAIN;
+    EXPECT(plan[NOC_PLAN_FAMILY] == r[5] && plan[NOC_PLAN_HEAVY] == r[6] && m[NOC_PLAN_WPS] == r[7] &&
+           m[NOC_PLAN_SPEC] == r[8] && m[NOC_PLAN_XLDS] == r[9] && m[NOC_PLAN_LDS] == r[10]);
+  }
+  EXPECT(plan[NOC_PLAN_INTS] == 12345);
   // round-4 building blocks: NULL family / pointers, bad sizes, misaligned, unknown flags; an
   // empty batch is a no-op
   double* ph = p + 1;  // misaligned for doubles
