@@ -3,7 +3,22 @@
  * (hipMalloc / torch data_ptr), row-major, contiguous, 16-byte aligned; every call is
  * asynchronous on `stream` (a hipStream_t, NULL = default stream) and never synchronises.
  *
- * Return value: 0 on success, < 0 on an argument or HIP error (noc_last_error() explains).
+ * Return value of the functions that return a status (noc_last_error() explains every code < 0;
+ * argument errors are reported before any device call; tests/test_abi_codes.py pins each one):
+ *     0   success, also for an empty batch (B or Bt = 0: validated, nothing launched)
+ *    -1   a bad value: unsupported family or (nx, nu), N < 1, batch < 0, illegal lanes, mode,
+ *         terminal, an undefined flag bit, bp0, max_solves / max_passes
+ *    -2   a required pointer (family, workspace, a workspace field, an array) is NULL
+ *    -3   a pointer is not aligned as its array needs (16, 8 or 4 bytes)
+ *   -10   a HIP error (launch or copy)
+ * The _params forms, noc_kkt_solve_compact and noc_blocks_expand report every argument error,
+ * NULL and misaligned pointers included, as -1; so do the noc_ipm_*_compact forms for a NULL
+ * family or workspace (their other checks are their dense twins', with the codes above) and
+ * noc_compact_width / noc_kkt_compact_keep.  A step form (noc_ipm_step, _compact, _params) passes
+ * on the code of its KKT solve, which checks the workspace's fields as its own arguments (so
+ * noc_ipm_step_params answers -3 for a misaligned workspace field).  The queries
+ * (noc_*_supported, noc_kkt_gains_on_chip) answer 0 instead; noc_kkt_pick_lanes,
+ * noc_tiled_doubles and noc_ddp_work_doubles answer -1 on bad dimensions.
  * Numerical trouble is data, never an error: feasible[b] = 0, pred NaN/inf, exactly like the
  * reference's jnp.where / NaN semantics (noc/par_interior_point_newton.py:159-173).
  *

@@ -376,9 +376,9 @@ bool ddp_params_supported(const noc_family& p) {
 }
 
 // tp: NULL, or the (Bt, 32) per-trajectory parameter records (ddp_params_supported families)
-static hipError_t ddp_launch(const noc_family& p, int N, int Bt, const double* x0, double* u,
-                             double* work, int* iterations, int* passes, int* done, double bp0,
-                             int max_passes, int flags, const double* tp, hipStream_t s) {
+hipError_t ddp_solve(const noc_family& p, int N, int Bt, const double* x0, double* u,
+                     double* work, int* iterations, int* passes, int* done, double bp0,
+                     int max_passes, int flags, const double* tp, hipStream_t s) {
   DdpArgs a{};
   a.one_stage = (flags & NOC_DDP_ONE_STAGE) ? 1 : 0;
   a.N = N;
@@ -413,21 +413,6 @@ static hipError_t ddp_launch(const noc_family& p, int N, int Bt, const double* x
     }
     return hipErrorInvalidValue;
   });
-}
-
-hipError_t ddp_solve(const noc_family& p, int N, int Bt, const double* x0, double* u,
-                     double* work, int* iterations, int* passes, int* done, double bp0,
-                     int max_passes, int flags, hipStream_t s) {
-  return ddp_launch(p, N, Bt, x0, u, work, iterations, passes, done, bp0, max_passes, flags,
-                    nullptr, s);
-}
-
-hipError_t ddp_solve_params(const noc_family& p, int N, int Bt, const double* x0, double* u,
-                            double* work, int* iterations, int* passes, int* done,
-                            const double* tp, double bp0, int max_passes, int flags,
-                            hipStream_t s) {
-  if (!tp || !ddp_params_supported(p)) return hipErrorInvalidValue;
-  return ddp_launch(p, N, Bt, x0, u, work, iterations, passes, done, bp0, max_passes, flags, tp, s);
 }
 
 }  // namespace noc

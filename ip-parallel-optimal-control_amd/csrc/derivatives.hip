@@ -105,12 +105,8 @@ static hipError_t launch_derivatives(const noc_family& p, const DerivArgs& a, hi
   });
 }
 
-hipError_t derivatives(const noc_family& p, const DerivArgs& a, hipStream_t s) {
-  return launch_derivatives(p, a, s);
-}
-
-hipError_t derivatives_params(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s) {
-  return launch_derivatives<TrajParams>(p, a, s, tp);
+hipError_t derivatives(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s) {
+  return !tp ? launch_derivatives(p, a, s) : launch_derivatives<TrajParams>(p, a, s, tp);
 }
 
 template <class... TP>
@@ -128,13 +124,9 @@ static hipError_t launch_final_derivs(const noc_family& p, int B, const double* 
 }
 
 hipError_t final_cost_derivs(const noc_family& p, int B, const double* xN, double* grad,
-                             double* hess, hipStream_t s) {
-  return launch_final_derivs(p, B, xN, grad, hess, s);
-}
-
-hipError_t final_cost_derivs_params(const noc_family& p, int B, const double* xN, double* grad,
-                                    double* hess, const double* tp, hipStream_t s) {
-  return launch_final_derivs<TrajParams>(p, B, xN, grad, hess, s, tp);
+                             double* hess, const double* tp, hipStream_t s) {
+  return !tp ? launch_final_derivs(p, B, xN, grad, hess, s)
+             : launch_final_derivs<TrajParams>(p, B, xN, grad, hess, s, tp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -176,13 +168,9 @@ static hipError_t launch_feasibility(const noc_family& p, int N, int B, const do
 }
 
 hipError_t traj_feasibility(const noc_family& p, int N, int B, const double* x, const double* u,
-                            int* ok, hipStream_t s) {
-  return launch_feasibility(p, N, B, x, u, ok, s);
-}
-
-hipError_t traj_feasibility_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                                   int* ok, const double* tp, hipStream_t s) {
-  return launch_feasibility<TrajParams>(p, N, B, x, u, ok, s, tp);
+                            int* ok, const double* tp, hipStream_t s) {
+  return !tp ? launch_feasibility(p, N, B, x, u, ok, s)
+             : launch_feasibility<TrajParams>(p, N, B, x, u, ok, s, tp);
 }
 
 // total_cost(x, u, bp) = final_cost(x_N) + sum_k stage_cost(x_k, u_k, bp) (PR:53-56, CR:48-51,
@@ -227,13 +215,9 @@ static hipError_t launch_total_cost(const noc_family& p, int N, int B, const dou
 }
 
 hipError_t total_cost(const noc_family& p, int N, int B, const double* x, const double* u,
-                      const double* bp, double* cost, hipStream_t s) {
-  return launch_total_cost(p, N, B, x, u, bp, cost, s);
-}
-
-hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                             const double* bp, double* cost, const double* tp, hipStream_t s) {
-  return launch_total_cost<TrajParams>(p, N, B, x, u, bp, cost, s, tp);
+                      const double* bp, double* cost, const double* tp, hipStream_t s) {
+  return !tp ? launch_total_cost(p, N, B, x, u, bp, cost, s)
+             : launch_total_cost<TrajParams>(p, N, B, x, u, bp, cost, s, tp);
 }
 
 // ------------------------------------------------------------------------------------------------

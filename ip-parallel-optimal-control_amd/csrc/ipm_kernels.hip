@@ -363,13 +363,29 @@ hipError_t ipm_promote(const noc_ipm_ws& w, hipStream_t s) {
 }
 
 // family dispatch (ipm_family.h: for_family): one instantiation per NOC_FAMILY line of families.def
+// Rollout (it takes no tp: it reads dt and the dynamics only), promote, then the main part.  The
+// families' dense and compact instances come first and the ones that take tp after them, in two
+// passes, so the unit's kernels keep their order.
 hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                       bool compact, hipStream_t s) {
+                       bool compact, const double* tp, hipStream_t s) {
+  if (tp && compact) return hipErrorInvalidValue;
+  const auto roll = [&](auto K, auto X, auto U) {
+    const hipError_t e = rollout_t<K, X, U>(p, w, s, 1);
+    if (e == hipSuccess) hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
+    return e;
+  };
+  if (!tp)
+    return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
+      const hipError_t e = roll(K, X, U);
+      return e != hipSuccess ? e : prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
+    });
   return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
-    hipError_t e = rollout_t<K, X, U>(p, w, s, 1);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
-    return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
+    if constexpr (traj_params_instance<K, X, U>()) {
+      const hipError_t e = roll(K, X, U);
+      return e != hipSuccess ? e : prepare_main_c<K, X, U, false, TrajParams>(p, w, mode, terminal, s, tp);
+    } else {
+      return hipErrorInvalidValue;
+    }
   });
 }
 
@@ -381,22 +397,6 @@ hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, 
                             bool compact, hipStream_t s) {
   return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
     return prepare_main_t<K, X, U>(p, w, mode, terminal, compact, s);
-  });
-}
-
-// per-trajectory cost parameters: the params form of prepare (the rollout needs none: it reads dt
-// and the dynamics only).  Dense blocks.
-hipError_t ipm_prepare_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                              int terminal, hipStream_t s) {
-  return for_family(p, hipErrorInvalidValue, [&](auto K, auto X, auto U) {
-    if constexpr (traj_params_instance<K, X, U>()) {
-      hipError_t e = rollout_t<K, X, U>(p, w, s, 1);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(promote_kernel, dim3((w.Bt + 255) / 256), dim3(256), 0, s, w);
-      return prepare_main_c<K, X, U, false, TrajParams>(p, w, mode, terminal, s, tp);
-    } else {
-      return hipErrorInvalidValue;
-    }
   });
 }
 
@@ -414,13 +414,9 @@ static hipError_t launch_trial(const noc_family& p, const noc_ipm_ws& w, int mod
   });
 }
 
-hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s) {
-  return launch_trial(p, w, mode, s);
-}
-
-hipError_t ipm_trial_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                            hipStream_t s) {
-  return launch_trial<TrajParams>(p, w, mode, s, tp);
+hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, const double* tp,
+                     hipStream_t s) {
+  return !tp ? launch_trial(p, w, mode, s) : launch_trial<TrajParams>(p, w, mode, s, tp);
 }
 
 hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s) {

@@ -257,7 +257,7 @@ bool ipm_solve_supported(const noc_family& p, int N, int lanes) {
 }
 
 // The plan of one solve call (ipm_plan.h) for the environment as it is now.  simds = 0: the
-// current device's (then 0 if none is visible); with_params: noc_ipm_solve_params.
+// current device's (then 0 if none is visible); with_params: a solve with tp.
 static PersistPlan ipm_plan(const noc_family& p, int N, int Bt, bool ordered, int flags, bool with_params,
                             int simds) {
   if (!family_supported(p) || (with_params && !traj_params_supported(p))) return PersistPlan{};
@@ -301,17 +301,11 @@ static hipError_t launch_plan(const PersistPlan& plan, const noc_ipm_ws& w, cons
   });
 }
 
-hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal, double bp0,
-                     int max_solves, hipStream_t s) {
-  const PersistPlan plan = ipm_plan(p, w.N, w.Bt, w.order != nullptr, w.flags, false, 0);
-  return launch_plan(plan, w, SolveArgs{p, nullptr, mode, terminal, bp0, max_solves}, s);
-}
-
-// Per-trajectory cost parameters (noc_ipm_solve_params): the plan never gives them the wide
+// tp (per-trajectory cost parameters, noc_ipm_solve_params): the plan never gives them the wide
 // kernel, speculative candidates or the heavy-first split (ipm_plan.h).
-hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                            int terminal, double bp0, int max_solves, hipStream_t s) {
-  const PersistPlan plan = ipm_plan(p, w.N, w.Bt, w.order != nullptr, w.flags, true, 0);
+hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal, double bp0,
+                     int max_solves, const double* tp, hipStream_t s) {
+  const PersistPlan plan = ipm_plan(p, w.N, w.Bt, w.order != nullptr, w.flags, tp != nullptr, 0);
   return launch_plan(plan, w, SolveArgs{p, tp, mode, terminal, bp0, max_solves}, s);
 }
 

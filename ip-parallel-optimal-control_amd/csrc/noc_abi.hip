@@ -3,6 +3,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/noc_hip.h"
@@ -36,14 +37,77 @@ int hip_status(hipError_t e, const char* where) {
   return fail(-10, std::string(where) + ": " + hipGetErrorString(e));
 }
 
+// ---- the argument rules, each written once -------------------------------------------------------
+struct Ptr {
+  const void* p;
+  const char* name;
+  bool required;
+  unsigned align = 16;
+};
+
+// in list order: the first offending pointer decides the code and the message
+int check_ptrs(std::initializer_list<Ptr> list) {
+  for (const Ptr& a : list)
+    if (int rc = check_ptr(a.p, a.name, a.required, a.align)) return rc;
+  return 0;
+}
+
+// ... every one required, under one name
+int check_all(std::initializer_list<const void*> list, const char* name, unsigned align) {
+  for (const void* p : list)
+    if (int rc = check_ptr(p, name, true, align)) return rc;
+  return 0;
+}
+
+// The _params and _compact forms report every argument error as -1 (include/noc_hip.h); a HIP
+// error stays -10.
+int args_as_minus1(int rc) { return rc < 0 && rc > -10 ? -1 : rc; }
+
+bool lanes_in(int lanes, std::initializer_list<int> legal) {
+  for (int l : legal)
+    if (lanes == l) return true;
+  return false;
+}
+
+int check_mode(int mode) {
+  return mode == NOC_MODE_PAR || mode == NOC_MODE_SEQ ? 0 : fail(-1, "bad mode");
+}
+
+int check_terminal(int terminal) {
+  return terminal == NOC_TERMINAL_FINAL_COST || terminal == NOC_TERMINAL_STAGE0
+             ? 0 : fail(-1, "bad terminal option");
+}
+
+constexpr int kWsFlagsAll = NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP;
+int check_ws_flags(int flags, const std::string& what) {
+  return flags & ~kWsFlagsAll ? fail(-1, what + " flags: unknown bits set (NOC_WS_ONE_STAGE | "
+                                                "NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP are defined)")
+                              : 0;
+}
+
+int check_family(const noc_family* fam) {
+  if (!fam) return fail(-2, "family is NULL");
+  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
+  return 0;
+}
+
+int check_horizon_batch(int N, int B) {
+  if (N < 1) return fail(-1, "horizon N must be >= 1");
+  if (B < 0) return fail(-1, "batch B must be >= 0");
+  return 0;
+}
+
+// the building blocks' sizes (N = 1 where the block has no horizon)
+int check_block_dims(int N, int B) {
+  return N < 1 || B < 0 ? fail(-1, "need N >= 1, B >= 0") : 0;
+}
+
 int check_dims(int nx, int nu, int N, int B, int lanes) {
   if (!noc::kkt_supported(nx, nu))
     return fail(-1, "unsupported (nx, nu) = (" + std::to_string(nx) + ", " + std::to_string(nu) +
                         "); supported: " + noc::kkt_shapes_str());
-  if (N < 1) return fail(-1, "horizon N must be >= 1");
-  if (B < 0) return fail(-1, "batch B must be >= 0");
-  if (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64 &&
-      lanes != 128)
+  if (int rc = check_horizon_batch(N, B)) return rc;
+  if (!lanes_in(lanes, {0, 1, 8, 16, 32, 64, 128}))
     return fail(-1, "lanes must be 0, 1, 8, 16, 32, 64 or 128");
   return 0;
 }
@@ -132,56 +196,31 @@ int noc_kkt_gains_on_chip(int nx, int nu, int N, int lanes) {
   return noc::kkt_lds_bytes_rt(nx, nu, N, L) > 0 ? 1 : 0;
 }
 
-static int kkt_common(int mode, int tiled, int nx, int nu, int N, int B, int lanes, const double* A,
-                      const double* Bm, const double* Q, const double* R, const double* M,
-                      const double* r, const double* q, const double* c, const double* P,
-                      const double* p, const double* x0, const double* reg, const int* active,
-                      double* dx, double* du, double* pred, int* feasible, double* K, double* d,
-                      double* S, double* v, void* stream) {
-  int rc = check_dims(nx, nu, N, B, lanes);
-  if (rc) return rc;
-  const bool bwd = mode != noc::MODE_FWD;
-  if ((rc = check_ptr(A, "A", true))) return rc;
-  if ((rc = check_ptr(Bm, "B", true))) return rc;
-  if ((rc = check_ptr(Q, "Q", bwd))) return rc;
-  if ((rc = check_ptr(R, "R", bwd))) return rc;
-  if ((rc = check_ptr(M, "M", bwd))) return rc;
-  if ((rc = check_ptr(r, "r", bwd))) return rc;
-  if ((rc = check_ptr(P, "P", bwd))) return rc;
-  if ((rc = check_ptr(q, "q", false))) return rc;
-  if ((rc = check_ptr(c, "c", false))) return rc;
-  if ((rc = check_ptr(p, "p", false))) return rc;
-  if ((rc = check_ptr(x0, "x0", false))) return rc;
-  if ((rc = check_ptr(K, "K", false))) return rc;
-  if ((rc = check_ptr(d, "d", false))) return rc;
-  if ((rc = check_ptr(S, "S", false))) return rc;
-  if ((rc = check_ptr(v, "v", false))) return rc;
-  if ((rc = check_ptr(dx, "dx", false))) return rc;
-  if ((rc = check_ptr(du, "du", false))) return rc;
-  if ((rc = check_ptr(reg, "reg", false, 8))) return rc;
-  if ((rc = check_ptr(pred, "pred", false, 8))) return rc;
-  if ((rc = check_ptr(feasible, "feasible", false, 4))) return rc;
-  if ((rc = check_ptr(active, "active", false, 4))) return rc;
-  if (B == 0) return 0;
-  noc::KKTArgs a{};
-  a.N = N;
-  a.B = B;
-  a.mode = mode;
-  a.A = A; a.Bm = Bm; a.Q = Q; a.R = R; a.M = M; a.r = r; a.q = q; a.c = c;
-  a.P = P; a.p = p; a.x0 = x0; a.reg = reg; a.active = active;
-  a.dx = dx; a.du = du; a.pred = pred; a.K = K; a.d = d; a.S = S; a.v = v;
-  a.feasible = feasible;
-  a.ablate = g_ablate;
-  a.tiled = tiled;
-  if (tiled && lanes == 0) return fail(-1, "the tiled layout needs an explicit lanes value");
-  if (tiled && lanes == 1 && !(nx == 8 && nu == 4))
+// the pointers of a KKT solve (bwd: it has a backward pass, which reads the cost blocks)
+static int check_kkt_ptrs(const noc::KKTArgs& a, bool bwd) {
+  return check_ptrs({{a.A, "A", true}, {a.Bm, "B", true}, {a.Q, "Q", bwd}, {a.R, "R", bwd},
+                     {a.M, "M", bwd}, {a.r, "r", bwd}, {a.P, "P", bwd}, {a.q, "q", false},
+                     {a.c, "c", false}, {a.p, "p", false}, {a.x0, "x0", false}, {a.K, "K", false},
+                     {a.d, "d", false}, {a.S, "S", false}, {a.v, "v", false}, {a.dx, "dx", false},
+                     {a.du, "du", false}, {a.reg, "reg", false, 8}, {a.pred, "pred", false, 8},
+                     {a.feasible, "feasible", false, 4}, {a.active, "active", false, 4}});
+}
+
+static const char kNeedGains[] = "K and d are required (workspace) unless noc_kkt_gains_on_chip() is 1";
+
+// a: N, B, mode, tiled and the pointers (KKTArgs order; the launcher sets the rest)
+static int kkt_run(int nx, int nu, int lanes, const noc::KKTArgs& a, void* stream) {
+  int rc = check_dims(nx, nu, a.N, a.B, lanes);
+  if (!rc) rc = check_kkt_ptrs(a, a.mode != noc::MODE_FWD);
+  if (rc || a.B == 0) return rc;
+  if (a.tiled && lanes == 0) return fail(-1, "the tiled layout needs an explicit lanes value");
+  if (a.tiled && lanes == 1 && !(nx == 8 && nu == 4))
     return fail(-1, "the grouped (lanes = 1) tiled layout is supported for (nx, nu) = (8, 4)");
   if (lanes == 1 && !(64 % nx == 0 && nu <= nx))
     return fail(-1, "the group solve (lanes = 1) needs nx dividing 64 and nu <= nx");
-  const int L = lanes ? lanes : noc::kkt_default_lanes(nx, nu, N);
-  const bool on_chip = mode == noc::MODE_FULL && (dx || du) && noc::kkt_lds_bytes_rt(nx, nu, N, L) > 0;
-  if ((!K || !d) && !on_chip)
-    return fail(-2, "K and d are required (workspace) unless noc_kkt_gains_on_chip() is 1");
+  const int L = lanes ? lanes : noc::kkt_default_lanes(nx, nu, a.N);
+  const bool on_chip = a.mode == noc::MODE_FULL && (a.dx || a.du) && noc::kkt_lds_bytes_rt(nx, nu, a.N, L) > 0;
+  if ((!a.K || !a.d) && !on_chip) return fail(-2, kNeedGains);
   return hip_status(noc::kkt_dispatch(nx, nu, a, L, static_cast<hipStream_t>(stream)),
                     "kkt_scan launch");
 }
@@ -192,8 +231,8 @@ int noc_kkt_solve(int nx, int nu, int N, int B, int lanes, const double* A, cons
                   const double* x0, const double* reg, const int* active, double* dx, double* du,
                   double* pred, int* feasible, double* K, double* d, double* S, double* v,
                   void* stream) {
-  return kkt_common(noc::MODE_FULL, 0, nx, nu, N, B, lanes, A, Bm, Q, R, M, r, q, c, P, p, x0, reg,
-                    active, dx, du, pred, feasible, K, d, S, v, stream);
+  return kkt_run(nx, nu, lanes, {N, B, noc::MODE_FULL, 0, A, Bm, Q, R, M, r, q, c, P, p, x0, reg, active,
+                                 dx, du, pred, K, d, S, v, feasible, g_ablate, 0}, stream);
 }
 
 int noc_kkt_solve_tiled(int nx, int nu, int N, int B, int lanes, const double* A,
@@ -202,8 +241,8 @@ int noc_kkt_solve_tiled(int nx, int nu, int N, int B, int lanes, const double* A
                         const double* p, const double* x0, const double* reg, const int* active,
                         double* dx, double* du, double* pred, int* feasible, double* K, double* d,
                         double* S, double* v, void* stream) {
-  return kkt_common(noc::MODE_FULL, 1, nx, nu, N, B, lanes, A, Bm, Q, R, M, r, q, c, P, p, x0,
-                    reg, active, dx, du, pred, feasible, K, d, S, v, stream);
+  return kkt_run(nx, nu, lanes, {N, B, noc::MODE_FULL, 0, A, Bm, Q, R, M, r, q, c, P, p, x0, reg, active,
+                                 dx, du, pred, K, d, S, v, feasible, g_ablate, 1}, stream);
 }
 
 int noc_kkt_compact_supported(const noc_family* fam, int N, int lanes) {
@@ -224,12 +263,25 @@ int noc_kkt_compact_keep(const noc_family* fam, int lanes) {
 // family / dims / lanes of the compact entry points (before any HIP call)
 static int check_compact_dims(const noc_family* fam, int N, int B, int lanes) {
   if (!fam) return fail(-1, "family is NULL");
-  if (N < 1) return fail(-1, "horizon N must be >= 1");
-  if (B < 0) return fail(-1, "batch B must be >= 0");
+  if (int rc = check_horizon_batch(N, B)) return rc;
   if (!noc::kkt_compact_supported(*fam, lanes))
     return fail(-1, "compact blocks: unsupported family or lanes (" + std::to_string(lanes) +
                         "); pendulum and cart-pole at lanes 8, 16, 32 or 64 (noc_kkt_compact_supported)");
   return 0;
+}
+
+// a: the tiled full solve of kkt_run without q, c, p, on compact A, B, Q, R, M
+static int kkt_compact_run(const noc_family* fam, int lanes, const noc::KKTArgs& a, void* stream) {
+  int rc = check_compact_dims(fam, a.N, a.B, lanes);
+  if (!rc) rc = check_kkt_ptrs(a, true);
+  if (!rc && a.B > 0) {
+    const bool on_chip = (a.dx || a.du) && noc::kkt_lds_bytes_rt(fam->nx, fam->nu, a.N, lanes) > 0;
+    rc = (!a.K || !a.d) && !on_chip
+             ? fail(-2, kNeedGains)
+             : hip_status(noc::kkt_compact_dispatch(*fam, a, lanes, static_cast<hipStream_t>(stream)),
+                          "kkt_scan_compact launch");
+  }
+  return args_as_minus1(rc);
 }
 
 int noc_kkt_solve_compact(const noc_family* fam, int N, int B, int lanes, const double* A,
@@ -237,45 +289,17 @@ int noc_kkt_solve_compact(const noc_family* fam, int N, int B, int lanes, const 
                           const double* r, const double* P, const double* x0, const double* reg,
                           const int* active, double* dx, double* du, double* pred, int* feasible,
                           double* K, double* d, double* S, double* v, void* stream) {
-  if (check_compact_dims(fam, N, B, lanes)) return -1;
-  const void* req[] = {A, Bm, Q, R, M, r, P};
-  const char* names[] = {"A", "B", "Q", "R", "M", "r", "P"};
-  for (int i = 0; i < 7; ++i)
-    if (check_ptr(req[i], names[i], true)) return -1;
-  if (check_ptr(x0, "x0", false) || check_ptr(K, "K", false) || check_ptr(d, "d", false) ||
-      check_ptr(S, "S", false) || check_ptr(v, "v", false) || check_ptr(dx, "dx", false) ||
-      check_ptr(du, "du", false) || check_ptr(reg, "reg", false, 8) ||
-      check_ptr(pred, "pred", false, 8) || check_ptr(feasible, "feasible", false, 4) ||
-      check_ptr(active, "active", false, 4))
-    return -1;
-  if (B == 0) return 0;
-  const int nx = fam->nx, nu = fam->nu;
-  const bool on_chip = (dx || du) && noc::kkt_lds_bytes_rt(nx, nu, N, lanes) > 0;
-  if ((!K || !d) && !on_chip) {
-    fail(-2, "K and d are required (workspace) unless noc_kkt_gains_on_chip() is 1");
-    return -1;
-  }
-  noc::KKTArgs a{};
-  a.N = N;
-  a.B = B;
-  a.mode = noc::MODE_FULL;
-  a.A = A; a.Bm = Bm; a.Q = Q; a.R = R; a.M = M; a.r = r;
-  a.P = P; a.x0 = x0; a.reg = reg; a.active = active;
-  a.dx = dx; a.du = du; a.pred = pred; a.K = K; a.d = d; a.S = S; a.v = v;
-  a.feasible = feasible;
-  a.ablate = g_ablate;
-  a.tiled = 1;
-  return hip_status(noc::kkt_compact_dispatch(*fam, a, lanes, static_cast<hipStream_t>(stream)),
-                    "kkt_scan_compact launch");
+  return kkt_compact_run(fam, lanes, {N, B, noc::MODE_FULL, 0, A, Bm, Q, R, M, r, nullptr, nullptr, P,
+                                      nullptr, x0, reg, active, dx, du, pred, K, d, S, v, feasible,
+                                      g_ablate, 1}, stream);
 }
 
 int noc_blocks_expand(const noc_family* fam, int N, int B, int lanes, const double* cA,
                       const double* cB, const double* cQ, const double* cR, const double* cM,
                       double* A, double* Bm, double* Q, double* R, double* M, void* stream) {
-  if (check_compact_dims(fam, N, B, lanes)) return -1;
-  const void* req[] = {cA, cB, cQ, cR, cM, A, Bm, Q, R, M};
-  for (const void* p : req)
-    if (check_ptr(p, "blocks_expand argument", true)) return -1;
+  if (check_compact_dims(fam, N, B, lanes) ||
+      check_all({cA, cB, cQ, cR, cM, A, Bm, Q, R, M}, "blocks_expand argument", 16))
+    return -1;
   if (B == 0) return 0;
   const noc::ExpandArgs e{N, B, lanes, cA, cB, cQ, cR, cM, A, Bm, Q, R, M};
   return hip_status(noc::blocks_expand(*fam, e, static_cast<hipStream_t>(stream)), "blocks_expand");
@@ -293,8 +317,7 @@ int noc_relayout(int direction, int E, int sym_n, int N, int B, int lanes, const
                  double* dst, void* stream) {
   if (direction != 0 && direction != 1) return fail(-1, "direction must be 0 or 1");
   if (N < 1 || B < 0 || E < 1) return fail(-1, "bad dims");
-  if (lanes != 1 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64 && lanes != 128)
-    return fail(-1, "lanes must be 1/8/16/32/64/128");
+  if (!lanes_in(lanes, {1, 8, 16, 32, 64, 128})) return fail(-1, "lanes must be 1/8/16/32/64/128");
   if (sym_n > 0 && E != sym_n * (sym_n + 1) / 2) return fail(-1, "E must be sym_n(sym_n+1)/2");
   if (!src || !dst) return fail(-2, "NULL pointer");
   return hip_status(noc::relayout(direction, E, sym_n, N, B, lanes, src, dst,
@@ -306,27 +329,28 @@ int noc_par_bwd_pass(int nx, int nu, int N, int B, int lanes, const double* A, c
                      const double* q, const double* c, const double* P, const double* p,
                      const double* reg, const int* active, double* K, double* d, double* S,
                      double* v, double* pred, int* feasible, void* stream) {
-  return kkt_common(noc::MODE_BWD, 0, nx, nu, N, B, lanes, A, Bm, Q, R, M, r, q, c, P, p, nullptr,
-                    reg, active, nullptr, nullptr, pred, feasible, K, d, S, v, stream);
+  return kkt_run(nx, nu, lanes, {N, B, noc::MODE_BWD, 0, A, Bm, Q, R, M, r, q, c, P, p, nullptr, reg,
+                                 active, nullptr, nullptr, pred, K, d, S, v, feasible, g_ablate, 0}, stream);
 }
 
 int noc_par_fwd_pass(int nx, int nu, int N, int B, int lanes, const double* A, const double* Bm,
                      const double* c, const double* x0, const double* K, const double* d,
                      const int* active, double* du, double* dx, void* stream) {
-  return kkt_common(noc::MODE_FWD, 0, nx, nu, N, B, lanes, A, Bm, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, c, nullptr, nullptr, x0, nullptr, active, dx, du, nullptr,
-                    nullptr, const_cast<double*>(K), const_cast<double*>(d), nullptr, nullptr,
-                    stream);
+  return kkt_run(nx, nu, lanes, {N, B, noc::MODE_FWD, 0, A, Bm, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 c, nullptr, nullptr, x0, nullptr, active, dx, du, nullptr,
+                                 const_cast<double*>(K), const_cast<double*>(d), nullptr, nullptr, nullptr,
+                                 g_ablate, 0}, stream);
 }
 
 int noc_family_supported(const noc_family* fam) {
   return (fam && noc::family_supported(*fam)) ? 1 : 0;
 }
 
+// fam: NULL where the entry point takes none
 static int check_ipm(const noc_family* fam, const noc_ipm_ws* ws) {
   if (!ws) return fail(-2, "workspace is NULL");
   if (ws->Bt < 0 || ws->N < 1) return fail(-1, "workspace dims: need Bt >= 0, N >= 1");
-  if (ws->lanes != 1 && ws->lanes != 8 && ws->lanes != 16 && ws->lanes != 32 && ws->lanes != 64)
+  if (!lanes_in(ws->lanes, {1, 8, 16, 32, 64}))
     return fail(-1, "workspace lanes must be 1, 8, 16, 32 or 64");
   if (ws->lanes == 1 && fam && !(fam->nx == 8 && fam->nu == 4))
     return fail(-1, "workspace lanes = 1 (grouped layout) is supported for nx = 8, nu = 4");
@@ -339,16 +363,18 @@ static int check_ipm(const noc_family* fam, const noc_ipm_ws* ws) {
                        ws->reg};
   for (const void* p : req)
     if (!p) return fail(-2, "a required workspace pointer is NULL");
-  if (ws->flags & ~(NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP))
-    return fail(-1, "workspace flags: unknown bits set (NOC_WS_ONE_STAGE | NOC_WS_RESUME | "
-                    "NOC_WS_NO_REPEAT_SKIP are defined)");
-  return 0;
+  return check_ws_flags(ws->flags, "workspace");
+}
+
+// ... of the entry points that take a family: it comes first
+static int check_fam_ipm(const noc_family* fam, const noc_ipm_ws* ws) {
+  if (!fam) return fail(-2, "family is NULL");
+  return check_ipm(fam, ws);
 }
 
 int noc_ipm_init(const noc_ipm_ws* ws, double bp0, void* stream) {
   int rc = check_ipm(nullptr, ws);
-  if (rc) return rc;
-  if (ws->Bt == 0) return 0;
+  if (rc || ws->Bt == 0) return rc;
   return hip_status(noc::ipm_init(*ws, bp0, static_cast<hipStream_t>(stream)), "ipm_init");
 }
 
@@ -359,108 +385,120 @@ static int check_compact(const noc_family* fam, const noc_ipm_ws* ws) {
   return 0;
 }
 
+// the _compact twins' first check
+static int check_both(const char* who, const noc_family* fam, const noc_ipm_ws* ws) {
+  return fam && ws ? 0 : fail(-1, std::string(who) + ": family or workspace is NULL");
+}
+
+// Below, one implementation per operation: `compact` = the workspace's blocks are the compact
+// fields, `params` = NULL or the per-trajectory records (never both).  The exported dense,
+// _compact and _params forms add their own first checks and code mapping.
+static int ipm_checks(const noc_family* fam, const noc_ipm_ws* ws, int mode, const int* terminal,
+                      bool compact) {
+  int rc = check_fam_ipm(fam, ws);
+  if (!rc && compact) rc = check_compact(fam, ws);
+  if (!rc) rc = check_mode(mode);
+  if (!rc && terminal) rc = check_terminal(*terminal);
+  return rc;
+}
+
 static int ipm_prepare_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
-                           bool compact, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  int rc = check_ipm(fam, ws);
+                           bool compact, const double* params, void* stream) {
+  int rc = ipm_checks(fam, ws, mode, &terminal, compact);
+  if (rc || ws->Bt == 0) return rc;
+  return hip_status(noc::ipm_prepare(*fam, *ws, mode, terminal, compact, params,
+                                     static_cast<hipStream_t>(stream)), "ipm_prepare");
+}
+
+static int ipm_trial_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, const double* params,
+                         void* stream) {
+  int rc = ipm_checks(fam, ws, mode, nullptr, false);
+  if (rc || ws->Bt == 0) return rc;
+  return hip_status(noc::ipm_trial(*fam, *ws, mode, params, static_cast<hipStream_t>(stream)),
+                    "ipm_trial");
+}
+
+// The KKT step of a workspace (active = phase SOLVE), then the trial.  The trial needs dx, du
+// only: the gains stay on chip when they fit (ws->K, ws->d otherwise).  The scan reads no cost
+// parameter (the blocks carry them); the trial does.
+static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, bool compact,
+                         const double* params, void* stream) {
+  const bool on_chip = noc_kkt_gains_on_chip(fam->nx, fam->nu, ws->N, ws->lanes) == 1;
+  const noc::KKTArgs a{ws->N, ws->Bt, noc::MODE_FULL, 0, ws->A, ws->B, ws->Q, ws->R, ws->M, ws->r, nullptr,
+                       nullptr, ws->P, nullptr, nullptr, ws->reg, ws->kkt_active, ws->dx, ws->du, ws->pred,
+                       on_chip ? nullptr : ws->K, on_chip ? nullptr : ws->d, nullptr, nullptr,
+                       ws->feasible, g_ablate, 1};
+  int rc = compact ? kkt_compact_run(fam, ws->lanes, a, stream)
+                   : kkt_run(fam->nx, fam->nu, ws->lanes, a, stream);
   if (rc) return rc;
-  if (compact && (rc = check_compact(fam, ws))) return rc;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
-    return fail(-1, "bad terminal option");
-  if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_prepare(*fam, *ws, mode, terminal, compact, static_cast<hipStream_t>(stream)),
-                    "ipm_prepare");
+  return ipm_trial_any(fam, ws, mode, params, stream);
+}
+
+// lanes of the step forms: 0 = the workspace's; any other value must equal it (the blocks are
+// laid out for it)
+static int check_step_lanes(const char* who, const noc_ipm_ws* ws, int lanes) {
+  if (ws && lanes != 0 && lanes != ws->lanes)
+    return fail(-1, std::string(who) + ": lanes (" + std::to_string(lanes) + ") differs from the workspace's (" +
+                        std::to_string(ws->lanes) + "); pass 0 or ws->lanes");
+  return 0;
+}
+
+static int ipm_step_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                        bool compact, const double* params, void* stream) {
+  int rc = ipm_prepare_any(fam, ws, mode, terminal, compact, params, stream);
+  if (rc) return rc;
+  return kkt_and_trial(fam, ws, mode, compact, params, stream);
+}
+
+static int ipm_step_main_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                             bool compact, void* stream) {
+  int rc = ipm_checks(fam, ws, mode, &terminal, compact);
+  if (rc || ws->Bt == 0) return rc;
+  rc = hip_status(noc::ipm_prepare_main(*fam, *ws, mode, terminal, compact,
+                                        static_cast<hipStream_t>(stream)), "ipm_prepare_main");
+  if (rc) return rc;
+  return kkt_and_trial(fam, ws, mode, compact, nullptr, stream);
 }
 
 int noc_ipm_prepare(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
                     void* stream) {
-  return ipm_prepare_any(fam, ws, mode, terminal, false, stream);
+  return ipm_prepare_any(fam, ws, mode, terminal, false, nullptr, stream);
 }
 
 int noc_ipm_prepare_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
                             void* stream) {
-  if (!fam || !ws) return fail(-1, "noc_ipm_prepare_compact: family or workspace is NULL");
-  return ipm_prepare_any(fam, ws, mode, terminal, true, stream);
+  if (int rc = check_both("noc_ipm_prepare_compact", fam, ws)) return rc;
+  return ipm_prepare_any(fam, ws, mode, terminal, true, nullptr, stream);
 }
 
 int noc_ipm_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  int rc = check_ipm(fam, ws);
-  if (rc) return rc;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_trial(*fam, *ws, mode, static_cast<hipStream_t>(stream)), "ipm_trial");
-}
-
-int noc_total_cost(const noc_family* fam, int N, int B, const double* x, const double* u,
-                   const double* bp, double* cost, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  int rc = 0;
-  if ((rc = check_ptr(x, "x", true, 8)) || (rc = check_ptr(u, "u", true, 8)) ||
-      (rc = check_ptr(bp, "bp", true, 8)) || (rc = check_ptr(cost, "cost", true, 8)))
-    return rc;
-  if (B == 0) return 0;
-  return hip_status(noc::total_cost(*fam, N, B, x, u, bp, cost, static_cast<hipStream_t>(stream)),
-                    "total_cost");
-}
-
-static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, bool compact,
-                         void* stream);
-
-static int ipm_step_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
-                        int lanes, bool compact, void* stream) {
-  // lanes: 0 = the workspace's; any other value must equal it (the blocks are laid out for it)
-  if (ws && lanes != 0 && lanes != ws->lanes)
-    return fail(-1, "noc_ipm_step: lanes (" + std::to_string(lanes) + ") differs from the workspace's (" +
-                        std::to_string(ws->lanes) + "); pass 0 or ws->lanes");
-  int rc = ipm_prepare_any(fam, ws, mode, terminal, compact, stream);
-  if (rc) return rc;
-  return kkt_and_trial(fam, ws, mode, compact, stream);
+  return ipm_trial_any(fam, ws, mode, nullptr, stream);
 }
 
 int noc_ipm_step(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, int lanes,
                  void* stream) {
-  return ipm_step_any(fam, ws, mode, terminal, lanes, false, stream);
+  if (int rc = check_step_lanes("noc_ipm_step", ws, lanes)) return rc;
+  return ipm_step_any(fam, ws, mode, terminal, false, nullptr, stream);
 }
 
 int noc_ipm_step_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
                          int lanes, void* stream) {
-  if (!fam || !ws) return fail(-1, "noc_ipm_step_compact: family or workspace is NULL");
-  return ipm_step_any(fam, ws, mode, terminal, lanes, true, stream);
+  int rc = check_both("noc_ipm_step_compact", fam, ws);
+  if (!rc) rc = check_step_lanes("noc_ipm_step", ws, lanes);
+  if (rc) return rc;
+  return ipm_step_any(fam, ws, mode, terminal, true, nullptr, stream);
 }
 
 int noc_ipm_rollout(const noc_family* fam, const noc_ipm_ws* ws, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  int rc = check_ipm(fam, ws);
-  if (rc) return rc;
-  if (ws->Bt == 0) return 0;
+  int rc = check_fam_ipm(fam, ws);
+  if (rc || ws->Bt == 0) return rc;
   return hip_status(noc::ipm_rollout(*fam, *ws, static_cast<hipStream_t>(stream)), "ipm_rollout");
 }
 
 int noc_ipm_promote(const noc_ipm_ws* ws, void* stream) {
   int rc = check_ipm(nullptr, ws);
-  if (rc) return rc;
-  if (ws->Bt == 0) return 0;
+  if (rc || ws->Bt == 0) return rc;
   return hip_status(noc::ipm_promote(*ws, static_cast<hipStream_t>(stream)), "ipm_promote");
-}
-
-static int ipm_step_main_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
-                             bool compact, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  int rc = check_ipm(fam, ws);
-  if (rc) return rc;
-  if (compact && (rc = check_compact(fam, ws))) return rc;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
-    return fail(-1, "bad terminal option");
-  if (ws->Bt == 0) return 0;
-  rc = hip_status(noc::ipm_prepare_main(*fam, *ws, mode, terminal, compact,
-                                        static_cast<hipStream_t>(stream)), "ipm_prepare_main");
-  if (rc) return rc;
-  return kkt_and_trial(fam, ws, mode, compact, stream);
 }
 
 int noc_ipm_step_main(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
@@ -470,7 +508,7 @@ int noc_ipm_step_main(const noc_family* fam, const noc_ipm_ws* ws, int mode, int
 
 int noc_ipm_step_main_compact(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
                               void* stream) {
-  if (!fam || !ws) return fail(-1, "noc_ipm_step_main_compact: family or workspace is NULL");
+  if (int rc = check_both("noc_ipm_step_main_compact", fam, ws)) return rc;
   return ipm_step_main_any(fam, ws, mode, terminal, true, stream);
 }
 
@@ -497,22 +535,23 @@ int noc_ipm_solve_supported(const noc_family* fam, int N, int lanes) {
   return (fam && N >= 1 && noc::ipm_solve_supported(*fam, N, lanes)) ? 1 : 0;
 }
 
-int noc_ipm_solve(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, double bp0,
-                  int max_solves, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  int rc = check_ipm(fam, ws);
+static int ipm_solve_any(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal,
+                         double bp0, int max_solves, const double* params, void* stream) {
+  int rc = ipm_checks(fam, ws, mode, &terminal, false);
   if (rc) return rc;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
-    return fail(-1, "bad terminal option");
   if (!(bp0 > 0.0)) return fail(-1, "bp0 must be > 0");
   if (max_solves < 1) return fail(-1, "max_solves must be >= 1");
   if (!noc::ipm_solve_supported(*fam, ws->N, ws->lanes))
     return fail(-1, "persistent solve needs workspace lanes = 64 and a step that fits in LDS "
                     "(noc_ipm_solve_supported)");
   if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_solve(*fam, *ws, mode, terminal, bp0, max_solves,
+  return hip_status(noc::ipm_solve(*fam, *ws, mode, terminal, bp0, max_solves, params,
                                    static_cast<hipStream_t>(stream)), "ipm_solve");
+}
+
+int noc_ipm_solve(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, double bp0,
+                  int max_solves, void* stream) {
+  return ipm_solve_any(fam, ws, mode, terminal, bp0, max_solves, nullptr, stream);
 }
 
 int noc_debug_ipm_plan(const noc_family* fam, int N, int Bt, int flags, int ordered, int with_params,
@@ -520,8 +559,7 @@ int noc_debug_ipm_plan(const noc_family* fam, int N, int Bt, int flags, int orde
   if (!fam || !out) return fail(-2, "noc_debug_ipm_plan: family or out is NULL");
   if (n < NOC_PLAN_INTS) return fail(-1, "noc_debug_ipm_plan: out needs NOC_PLAN_INTS entries");
   if (N < 1 || Bt < 0 || simds < 0) return fail(-1, "noc_debug_ipm_plan: need N >= 1, Bt >= 0, simds >= 0");
-  if (flags & ~(NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP))
-    return fail(-1, "noc_debug_ipm_plan: unknown flags bits set");
+  if (int rc = check_ws_flags(flags, "noc_debug_ipm_plan:")) return rc;
   noc::debug_ipm_plan(*fam, N, Bt, flags, ordered != 0, with_params != 0, simds, out);
   return 0;
 }
@@ -535,35 +573,40 @@ long long noc_ddp_work_doubles(int nx, int nu, int N, int Bt) {
 
 int noc_ddp_supported(const noc_family* fam) { return (fam && noc::ddp_supported(*fam)) ? 1 : 0; }
 
-int noc_ddp_solve(const noc_family* fam, int N, int Bt, const double* x0, double* u, double* work,
-                  int* iterations, int* passes, int* done, double bp0, int max_passes,
-                  void* stream) {
-  return noc_ddp_solve_ex(fam, N, Bt, x0, u, work, iterations, passes, done, bp0, max_passes, 0,
-                          stream);
-}
-
-int noc_ddp_solve_ex(const noc_family* fam, int N, int Bt, const double* x0, double* u,
-                     double* work, int* iterations, int* passes, int* done, double bp0,
-                     int max_passes, int flags, void* stream) {
+static int ddp_solve_any(const noc_family* fam, int N, int Bt, const double* x0, double* u,
+                         double* work, int* iterations, int* passes, int* done, double bp0,
+                         int max_passes, int flags, const double* params, void* stream) {
   if (flags & ~NOC_DDP_ONE_STAGE) return fail(-1, "ddp flags: only NOC_DDP_ONE_STAGE is defined");
   if (!fam) return fail(-2, "family is NULL");
   if (!noc::ddp_supported(*fam))
     return fail(-1, "DDP supports the registered families with nx <= 4 (noc_ddp_supported)");
-  if (N < 1) return fail(-1, "horizon N must be >= 1");
-  if (Bt < 0) return fail(-1, "batch Bt must be >= 0");
+  if (int rc = check_horizon_batch(N, Bt)) return rc;
   // any finite bp0 >= 0, like the reference ddp (D:98, no check on bp): bp0 = 0 is the
   // unconstrained one-stage solve; the schedule (no NOC_DDP_ONE_STAGE) runs no stage for
   // bp0 <= 1e-4, as interior_point_ddp's while loop (D:194) -- the same rule as the nx > 4 host loop
   if (!(bp0 >= 0.0) || !(bp0 < INFINITY)) return fail(-1, "bp0 must be finite and >= 0");
   if (max_passes < 1) return fail(-1, "max_passes must be >= 1");
-  int rc = 0;
-  if ((rc = check_ptr(x0, "x0", true, 8)) || (rc = check_ptr(u, "u", true, 8)) ||
-      (rc = check_ptr(work, "work", true, 8)) || (rc = check_ptr(iterations, "iterations", true, 4)) ||
-      (rc = check_ptr(passes, "passes", true, 4)) || (rc = check_ptr(done, "done", true, 4)))
-    return rc;
-  if (Bt == 0) return 0;
+  int rc = check_ptrs({{x0, "x0", true, 8}, {u, "u", true, 8}, {work, "work", true, 8},
+                       {iterations, "iterations", true, 4}, {passes, "passes", true, 4},
+                       {done, "done", true, 4}});
+  if (rc || Bt == 0) return rc;
   return hip_status(noc::ddp_solve(*fam, N, Bt, x0, u, work, iterations, passes, done, bp0,
-                                   max_passes, flags, static_cast<hipStream_t>(stream)), "ddp_solve");
+                                   max_passes, flags, params, static_cast<hipStream_t>(stream)),
+                    "ddp_solve");
+}
+
+int noc_ddp_solve(const noc_family* fam, int N, int Bt, const double* x0, double* u, double* work,
+                  int* iterations, int* passes, int* done, double bp0, int max_passes,
+                  void* stream) {
+  return ddp_solve_any(fam, N, Bt, x0, u, work, iterations, passes, done, bp0, max_passes, 0,
+                       nullptr, stream);
+}
+
+int noc_ddp_solve_ex(const noc_family* fam, int N, int Bt, const double* x0, double* u,
+                     double* work, int* iterations, int* passes, int* done, double bp0,
+                     int max_passes, int flags, void* stream) {
+  return ddp_solve_any(fam, N, Bt, x0, u, work, iterations, passes, done, bp0, max_passes, flags,
+                       nullptr, stream);
 }
 
 int noc_ddp_bwd_pass(int nx, int nu, int N, int B, const double* Vx, const double* Vxx,
@@ -573,16 +616,11 @@ int noc_ddp_bwd_pass(int nx, int nu, int N, int B, const double* Vx, const doubl
                      double* k, double* K, double* pred, int* feasible, double* Hu, void* stream) {
   if (!noc::kkt_supported(nx, nu))
     return fail(-1, "noc_ddp_bwd_pass: unsupported (nx, nu); supported: " + noc::kkt_shapes_str());
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  const void* req[] = {Vx, Vxx, reg_param, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu, k, K,
-                       pred, Hu};
-  for (const void* p : req) {
-    int rc = check_ptr(p, "ddp_bwd_pass argument", true, 8);
-    if (rc) return rc;
-  }
-  int rc = check_ptr(feasible, "feasible", true, 4);
-  if (rc) return rc;
-  if (B == 0) return 0;
+  int rc = check_block_dims(N, B);
+  if (!rc) rc = check_all({Vx, Vxx, reg_param, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu, k, K, pred, Hu},
+                          "ddp_bwd_pass argument", 8);
+  if (!rc) rc = check_ptrs({{feasible, "feasible", true, 4}});
+  if (rc || B == 0) return rc;
   noc::DdpBwdArgs a{N, B, Vx, Vxx, reg_param, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu,
                     k, K, pred, Hu, feasible};
   return hip_status(noc::ddp_bwd_pass(nx, nu, a, static_cast<hipStream_t>(stream)), "ddp_bwd_pass");
@@ -591,59 +629,85 @@ int noc_ddp_bwd_pass(int nx, int nu, int N, int B, const double* Vx, const doubl
 int noc_nonlin_rollout(const noc_family* fam, int N, int B, const double* K, const double* k,
                        const double* x, const double* u, double* x_new, double* u_new,
                        void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  const void* req[] = {K, k, x, u, x_new, u_new};
-  for (const void* p : req) {
-    int rc = check_ptr(p, "nonlin_rollout argument", true, 8);
-    if (rc) return rc;
-  }
-  if (B == 0) return 0;
+  int rc = check_family(fam);
+  if (!rc) rc = check_block_dims(N, B);
+  if (!rc) rc = check_all({K, k, x, u, x_new, u_new}, "nonlin_rollout argument", 8);
+  if (rc || B == 0) return rc;
   return hip_status(noc::nonlin_rollout(*fam, N, B, K, k, x, u, x_new, u_new,
                                         static_cast<hipStream_t>(stream)), "nonlin_rollout");
+}
+
+// The building blocks that read a cost parameter, each with its _params twin further down.
+static int derivatives_any(const noc_family* fam, const noc::DerivArgs& a, const double* params,
+                           void* stream) {
+  int rc = check_family(fam);
+  if (!rc) rc = check_block_dims(a.N, a.B);
+  if (!rc) rc = check_all({a.x, a.u, a.bp, a.cx, a.cu, a.cxx, a.cuu, a.cxu, a.fx, a.fu, a.fxx, a.fuu, a.fxu},
+                          "derivatives argument", 8);
+  if (rc || a.B == 0) return rc;
+  return hip_status(noc::derivatives(*fam, a, params, static_cast<hipStream_t>(stream)), "derivatives");
+}
+
+static int final_cost_derivs_any(const noc_family* fam, int B, const double* xN, double* grad,
+                                 double* hess, const double* params, void* stream) {
+  int rc = check_family(fam);
+  if (!rc) rc = check_block_dims(1, B);
+  if (!rc) rc = check_ptrs({{xN, "xN", true, 8}, {grad, "grad", true, 8}, {hess, "hess", false, 8}});
+  if (rc || B == 0) return rc;
+  return hip_status(noc::final_cost_derivs(*fam, B, xN, grad, hess, params,
+                                           static_cast<hipStream_t>(stream)), "final_cost_derivs");
+}
+
+static int check_feasibility_any(const noc_family* fam, int N, int B, const double* x, const double* u,
+                                 int* feasible, const double* params, void* stream) {
+  int rc = check_family(fam);
+  if (!rc) rc = check_block_dims(N, B);
+  if (!rc) rc = check_ptrs({{x, "x", true, 8}, {u, "u", true, 8}, {feasible, "feasible", true, 4}});
+  if (rc || B == 0) return rc;
+  return hip_status(noc::traj_feasibility(*fam, N, B, x, u, feasible, params,
+                                          static_cast<hipStream_t>(stream)), "check_feasibility");
+}
+
+static int total_cost_any(const noc_family* fam, int N, int B, const double* x, const double* u,
+                          const double* bp, double* cost, const double* params, void* stream) {
+  int rc = check_family(fam);
+  if (!rc) rc = check_block_dims(N, B);
+  if (!rc) rc = check_ptrs({{x, "x", true, 8}, {u, "u", true, 8}, {bp, "bp", true, 8}, {cost, "cost", true, 8}});
+  if (rc || B == 0) return rc;
+  return hip_status(noc::total_cost(*fam, N, B, x, u, bp, cost, params, static_cast<hipStream_t>(stream)),
+                    "total_cost");
 }
 
 int noc_derivatives(const noc_family* fam, int N, int B, const double* x, const double* u,
                     const double* bp, double* cx, double* cu, double* cxx, double* cuu,
                     double* cxu, double* fx, double* fu, double* fxx, double* fuu, double* fxu,
                     void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  const void* req[] = {x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
-  for (const void* p : req) {
-    int rc = check_ptr(p, "derivatives argument", true, 8);
-    if (rc) return rc;
-  }
-  if (B == 0) return 0;
-  noc::DerivArgs a{N, B, x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
-  return hip_status(noc::derivatives(*fam, a, static_cast<hipStream_t>(stream)), "derivatives");
+  return derivatives_any(fam, {N, B, x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu}, nullptr,
+                         stream);
 }
 
 int noc_final_cost_derivs(const noc_family* fam, int B, const double* xN, double* grad,
                           double* hess, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
-  if (B < 0) return fail(-1, "need B >= 0");
-  int rc = 0;
-  if ((rc = check_ptr(xN, "xN", true, 8)) || (rc = check_ptr(grad, "grad", true, 8)) ||
-      (rc = check_ptr(hess, "hess", false, 8)))
-    return rc;
-  if (B == 0) return 0;
-  return hip_status(noc::final_cost_derivs(*fam, B, xN, grad, hess, static_cast<hipStream_t>(stream)),
-                    "final_cost_derivs");
+  return final_cost_derivs_any(fam, B, xN, grad, hess, nullptr, stream);
+}
+
+int noc_check_feasibility(const noc_family* fam, int N, int B, const double* x, const double* u,
+                          int* feasible, void* stream) {
+  return check_feasibility_any(fam, N, B, x, u, feasible, nullptr, stream);
+}
+
+int noc_total_cost(const noc_family* fam, int N, int B, const double* x, const double* u,
+                   const double* bp, double* cost, void* stream) {
+  return total_cost_any(fam, N, B, x, u, bp, cost, nullptr, stream);
 }
 
 int noc_costates(int nx, int N, int B, const double* lamT, const double* cx, const double* fx,
                  double* lam, int sequential, void* stream) {
   if (nx < 1 || nx > 8) return fail(-1, "costates support 1 <= nx <= 8");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  int rc = 0;
-  if ((rc = check_ptr(lamT, "lamT", true, 8)) || (rc = check_ptr(cx, "cx", true, 8)) ||
-      (rc = check_ptr(fx, "fx", true, 8)) || (rc = check_ptr(lam, "lam", true, 8)))
-    return rc;
-  if (B == 0) return 0;
+  int rc = check_block_dims(N, B);
+  if (!rc) rc = check_ptrs({{lamT, "lamT", true, 8}, {cx, "cx", true, 8}, {fx, "fx", true, 8},
+                            {lam, "lam", true, 8}});
+  if (rc || B == 0) return rc;
   return hip_status(noc::costates(nx, N, B, lamT, cx, fx, lam, sequential,
                                   static_cast<hipStream_t>(stream)), "costates");
 }
@@ -653,73 +717,39 @@ int noc_lqr_params(int nx, int nu, int N, int B, const double* lam, const double
                    const double* fxx, const double* fuu, const double* fxu, double* ru, double* Q,
                    double* R, double* M, void* stream) {
   if (nx < 1 || nx > 8 || nu < 1 || nu > 8) return fail(-1, "lqr_params support nx, nu <= 8");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  const void* req[] = {lam, cu, cxx, cuu, cxu, fu, fxx, fuu, fxu, ru, Q, R, M};
-  for (const void* p : req) {
-    int rc = check_ptr(p, "lqr_params argument", true, 8);
-    if (rc) return rc;
-  }
-  if (B == 0) return 0;
+  int rc = check_block_dims(N, B);
+  if (!rc) rc = check_all({lam, cu, cxx, cuu, cxu, fu, fxx, fuu, fxu, ru, Q, R, M}, "lqr_params argument", 8);
+  if (rc || B == 0) return rc;
   noc::LqrArgs a{nx, nu, N, B, lam, cu, cxx, cuu, cxu, fu, fxx, fuu, fxu, ru, Q, R, M};
   return hip_status(noc::lqr_params(a, static_cast<hipStream_t>(stream)), "lqr_params");
-}
-
-int noc_check_feasibility(const noc_family* fam, int N, int B, const double* x, const double* u,
-                          int* feasible, void* stream) {
-  if (!fam) return fail(-2, "family is NULL");
-  if (!noc::family_supported(*fam)) return fail(-1, "unsupported problem family (kind/nx/nu)");
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  int rc = 0;
-  if ((rc = check_ptr(x, "x", true, 8)) || (rc = check_ptr(u, "u", true, 8)) ||
-      (rc = check_ptr(feasible, "feasible", true, 4)))
-    return rc;
-  if (B == 0) return 0;
-  return hip_status(noc::traj_feasibility(*fam, N, B, x, u, feasible,
-                                          static_cast<hipStream_t>(stream)), "check_feasibility");
-}
-
-static int kkt_and_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, bool compact,
-                         void* stream) {
-  // the trial step needs dx, du only: gains stay on chip when they fit (ws->K, ws->d otherwise)
-  const bool on_chip = noc_kkt_gains_on_chip(fam->nx, fam->nu, ws->N, ws->lanes) == 1;
-  if (compact) {
-    int rc = noc_kkt_solve_compact(fam, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q, ws->R, ws->M,
-                                   ws->r, ws->P, nullptr, ws->reg, ws->kkt_active, ws->dx, ws->du,
-                                   ws->pred, ws->feasible, on_chip ? nullptr : ws->K,
-                                   on_chip ? nullptr : ws->d, nullptr, nullptr, stream);
-    if (rc) return rc;
-    return noc_ipm_trial(fam, ws, mode, stream);
-  }
-  int rc = noc_kkt_solve_tiled(fam->nx, fam->nu, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q,
-                               ws->R, ws->M, ws->r, nullptr, nullptr, ws->P, nullptr, nullptr,
-                               ws->reg, ws->kkt_active, ws->dx, ws->du, ws->pred, ws->feasible,
-                               on_chip ? nullptr : ws->K, on_chip ? nullptr : ws->d, nullptr,
-                               nullptr, stream);
-  if (rc) return rc;
-  return noc_ipm_trial(fam, ws, mode, stream);
 }
 
 // ---- per-trajectory cost parameters (include/noc_hip.h) ----------------------------------------
 int noc_traj_params_supported(const noc_family* fam, int N, int lanes) {
   if (!fam || N < 1 || !noc::traj_params_supported(*fam)) return 0;
   if (lanes == 1) return (fam->nx == 8 && fam->nu == 4) ? 1 : 0;  // grouped layout (check_ipm)
-  return (lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64) ? 1 : 0;
+  return lanes_in(lanes, {8, 16, 32, 64}) ? 1 : 0;
 }
 
-// the argument errors of the _params entry points, all -1, before any device call
+// the params record pointer and the family's parametrised cost (w: "<entry point>: ")
+static int check_params_ptr(const std::string& w, const noc_family* fam, const double* params) {
+  if (!params) return fail(-1, w + "params is NULL (one record of 32 doubles per trajectory)");
+  if (reinterpret_cast<uintptr_t>(params) & 15) return fail(-1, w + "params not 16-byte aligned");
+  if (!noc::traj_params_supported(*fam))
+    return fail(-1, w + "unsupported family (unknown kind / nx / nu, or a registered family with "
+                        "traced costs, which has no goal / weights / bound)");
+  return 0;
+}
+
+// the argument errors of the noc_ipm_*_params entry points, all -1, before any device call
 static int check_params(const char* who, const noc_family* fam, const noc_ipm_ws* ws,
                         const double* params) {
-  const std::string w(who);
-  if (!fam || !ws) return fail(-1, w + ": family or workspace is NULL");
-  if (!params) return fail(-1, w + ": params is NULL (one record of 32 doubles per trajectory)");
-  if (reinterpret_cast<uintptr_t>(params) & 15) return fail(-1, w + ": params not 16-byte aligned");
-  if (!noc::traj_params_supported(*fam))
-    return fail(-1, w + ": unsupported family (unknown kind / nx / nu, or a registered family with "
-                        "traced costs, which has no goal / weights / bound)");
-  if (ws->flags & ~(NOC_WS_ONE_STAGE | NOC_WS_RESUME | NOC_WS_NO_REPEAT_SKIP))
-    return fail(-1, w + ": workspace flags: unknown bits set");
+  const std::string w = std::string(who) + ": ";
+  if (check_both(who, fam, ws) || check_params_ptr(w, fam, params) ||
+      check_ws_flags(ws->flags, w + "workspace"))
+    return -1;
   if (!noc_traj_params_supported(fam, ws->N, ws->lanes))
-    return fail(-1, w + ": wrong lanes (" + std::to_string(ws->lanes) + ") or horizon for this family "
+    return fail(-1, w + "wrong lanes (" + std::to_string(ws->lanes) + ") or horizon for this family "
                         "(noc_traj_params_supported)");
   return check_ipm(fam, ws) ? -1 : 0;
 }
@@ -727,39 +757,21 @@ static int check_params(const char* who, const noc_family* fam, const noc_ipm_ws
 int noc_ipm_prepare_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
                            int mode, int terminal, void* stream) {
   if (check_params("noc_ipm_prepare_params", fam, ws, params)) return -1;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
-    return fail(-1, "bad terminal option");
-  if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_prepare_params(*fam, *ws, params, mode, terminal,
-                                            static_cast<hipStream_t>(stream)), "ipm_prepare_params");
+  return args_as_minus1(ipm_prepare_any(fam, ws, mode, terminal, false, params, stream));
 }
 
 int noc_ipm_trial_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
                          int mode, void* stream) {
   if (check_params("noc_ipm_trial_params", fam, ws, params)) return -1;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_trial_params(*fam, *ws, params, mode, static_cast<hipStream_t>(stream)),
-                    "ipm_trial_params");
+  return args_as_minus1(ipm_trial_any(fam, ws, mode, params, stream));
 }
 
+// (the KKT step's own codes pass through: -3 for a misaligned workspace field)
 int noc_ipm_step_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
                         int mode, int terminal, int lanes, void* stream) {
-  if (ws && lanes != 0 && lanes != ws->lanes)
-    return fail(-1, "noc_ipm_step_params: lanes (" + std::to_string(lanes) + ") differs from the "
-                    "workspace's (" + std::to_string(ws->lanes) + "); pass 0 or ws->lanes");
-  int rc = noc_ipm_prepare_params(fam, ws, params, mode, terminal, stream);
-  if (rc) return rc;
-  // the dense KKT scan reads no cost parameter (the blocks carry them), then the params trial
-  const bool on_chip = noc_kkt_gains_on_chip(fam->nx, fam->nu, ws->N, ws->lanes) == 1;
-  rc = noc_kkt_solve_tiled(fam->nx, fam->nu, ws->N, ws->Bt, ws->lanes, ws->A, ws->B, ws->Q, ws->R,
-                           ws->M, ws->r, nullptr, nullptr, ws->P, nullptr, nullptr, ws->reg,
-                           ws->kkt_active, ws->dx, ws->du, ws->pred, ws->feasible,
-                           on_chip ? nullptr : ws->K, on_chip ? nullptr : ws->d, nullptr, nullptr,
-                           stream);
-  if (rc) return rc;
-  return noc_ipm_trial_params(fam, ws, params, mode, stream);
+  if (int rc = check_step_lanes("noc_ipm_step_params", ws, lanes)) return rc;
+  if (check_params("noc_ipm_step_params", fam, ws, params)) return -1;
+  return ipm_step_any(fam, ws, mode, terminal, false, params, stream);
 }
 
 int noc_ipm_solve_params(const noc_family* fam, const noc_ipm_ws* ws, const double* params,
@@ -768,17 +780,7 @@ int noc_ipm_solve_params(const noc_family* fam, const noc_ipm_ws* ws, const doub
     return fail(-1, "noc_ipm_solve_params: wrong lanes (" + std::to_string(ws->lanes) +
                         "): the persistent solve needs workspace lanes = 64");
   if (check_params("noc_ipm_solve_params", fam, ws, params)) return -1;
-  if (mode != NOC_MODE_PAR && mode != NOC_MODE_SEQ) return fail(-1, "bad mode");
-  if (terminal != NOC_TERMINAL_FINAL_COST && terminal != NOC_TERMINAL_STAGE0)
-    return fail(-1, "bad terminal option");
-  if (!(bp0 > 0.0)) return fail(-1, "bp0 must be > 0");
-  if (max_solves < 1) return fail(-1, "max_solves must be >= 1");
-  if (!noc::ipm_solve_supported(*fam, ws->N, ws->lanes))
-    return fail(-1, "noc_ipm_solve_params: unsupported family or horizon for the persistent solve "
-                    "(noc_ipm_solve_supported)");
-  if (ws->Bt == 0) return 0;
-  return hip_status(noc::ipm_solve_params(*fam, *ws, params, mode, terminal, bp0, max_solves,
-                                          static_cast<hipStream_t>(stream)), "ipm_solve_params");
+  return args_as_minus1(ipm_solve_any(fam, ws, mode, terminal, bp0, max_solves, params, stream));
 }
 
 // ---- per-trajectory cost parameters in interior-point DDP and the building blocks -------------
@@ -788,15 +790,11 @@ int noc_ddp_params_supported(const noc_family* fam) {
 
 // the errors the _params forms add to their twins', all -1, before any device call
 static int check_block_params(const char* who, const noc_family* fam, const double* params, bool ddp) {
-  const std::string w(who);
-  if (!fam) return fail(-1, w + ": family is NULL");
-  if (!params) return fail(-1, w + ": params is NULL (one record of 32 doubles per trajectory)");
-  if (reinterpret_cast<uintptr_t>(params) & 15) return fail(-1, w + ": params not 16-byte aligned");
-  if (!noc::traj_params_supported(*fam))
-    return fail(-1, w + ": unsupported family (unknown kind / nx / nu, or a registered family with "
-                        "traced costs, which has no goal / weights / bound)");
+  const std::string w = std::string(who) + ": ";
+  if (!fam) return fail(-1, w + "family is NULL");
+  if (check_params_ptr(w, fam, params)) return -1;
   if (ddp && !noc::ddp_params_supported(*fam))
-    return fail(-1, w + ": unsupported family for the one-launch DDP kernel: nx <= 4 "
+    return fail(-1, w + "unsupported family for the one-launch DDP kernel: nx <= 4 "
                         "(noc_ddp_params_supported)");
   return 0;
 }
@@ -805,19 +803,8 @@ int noc_ddp_solve_params(const noc_family* fam, int N, int Bt, const double* x0,
                          double* work, int* iterations, int* passes, int* done,
                          const double* params, double bp0, int max_passes, int flags, void* stream) {
   if (check_block_params("noc_ddp_solve_params", fam, params, true)) return -1;
-  if (flags & ~NOC_DDP_ONE_STAGE) return fail(-1, "ddp flags: only NOC_DDP_ONE_STAGE is defined");
-  if (N < 1) return fail(-1, "horizon N must be >= 1");
-  if (Bt < 0) return fail(-1, "batch Bt must be >= 0");
-  if (!(bp0 >= 0.0) || !(bp0 < INFINITY)) return fail(-1, "bp0 must be finite and >= 0");  // noc_ddp_solve_ex
-  if (max_passes < 1) return fail(-1, "max_passes must be >= 1");
-  if (check_ptr(x0, "x0", true, 8) || check_ptr(u, "u", true, 8) || check_ptr(work, "work", true, 8) ||
-      check_ptr(iterations, "iterations", true, 4) || check_ptr(passes, "passes", true, 4) ||
-      check_ptr(done, "done", true, 4))
-    return -1;
-  if (Bt == 0) return 0;
-  return hip_status(noc::ddp_solve_params(*fam, N, Bt, x0, u, work, iterations, passes, done, params,
-                                          bp0, max_passes, flags, static_cast<hipStream_t>(stream)),
-                    "ddp_solve_params");
+  return args_as_minus1(ddp_solve_any(fam, N, Bt, x0, u, work, iterations, passes, done, bp0,
+                                      max_passes, flags, params, stream));
 }
 
 int noc_derivatives_params(const noc_family* fam, int N, int B, const double* x, const double* u,
@@ -825,53 +812,27 @@ int noc_derivatives_params(const noc_family* fam, int N, int B, const double* x,
                            double* cxu, double* fx, double* fu, double* fxx, double* fuu,
                            double* fxu, const double* params, void* stream) {
   if (check_block_params("noc_derivatives_params", fam, params, false)) return -1;
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  const void* req[] = {x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
-  for (const void* p : req)
-    if (check_ptr(p, "derivatives argument", true, 8)) return -1;
-  if (B == 0) return 0;
-  noc::DerivArgs a{N, B, x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu};
-  return hip_status(noc::derivatives_params(*fam, a, params, static_cast<hipStream_t>(stream)),
-                    "derivatives_params");
+  return args_as_minus1(derivatives_any(
+      fam, {N, B, x, u, bp, cx, cu, cxx, cuu, cxu, fx, fu, fxx, fuu, fxu}, params, stream));
 }
 
 int noc_final_cost_derivs_params(const noc_family* fam, int B, const double* xN, double* grad,
                                  double* hess, const double* params, void* stream) {
   if (check_block_params("noc_final_cost_derivs_params", fam, params, false)) return -1;
-  if (B < 0) return fail(-1, "need B >= 0");
-  if (check_ptr(xN, "xN", true, 8) || check_ptr(grad, "grad", true, 8) ||
-      check_ptr(hess, "hess", false, 8))
-    return -1;
-  if (B == 0) return 0;
-  return hip_status(noc::final_cost_derivs_params(*fam, B, xN, grad, hess, params,
-                                                  static_cast<hipStream_t>(stream)),
-                    "final_cost_derivs_params");
+  return args_as_minus1(final_cost_derivs_any(fam, B, xN, grad, hess, params, stream));
 }
 
 int noc_check_feasibility_params(const noc_family* fam, int N, int B, const double* x,
                                  const double* u, int* feasible, const double* params,
                                  void* stream) {
   if (check_block_params("noc_check_feasibility_params", fam, params, false)) return -1;
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  if (check_ptr(x, "x", true, 8) || check_ptr(u, "u", true, 8) ||
-      check_ptr(feasible, "feasible", true, 4))
-    return -1;
-  if (B == 0) return 0;
-  return hip_status(noc::traj_feasibility_params(*fam, N, B, x, u, feasible, params,
-                                                 static_cast<hipStream_t>(stream)),
-                    "check_feasibility_params");
+  return args_as_minus1(check_feasibility_any(fam, N, B, x, u, feasible, params, stream));
 }
 
 int noc_total_cost_params(const noc_family* fam, int N, int B, const double* x, const double* u,
                           const double* bp, double* cost, const double* params, void* stream) {
   if (check_block_params("noc_total_cost_params", fam, params, false)) return -1;
-  if (N < 1 || B < 0) return fail(-1, "need N >= 1, B >= 0");
-  if (check_ptr(x, "x", true, 8) || check_ptr(u, "u", true, 8) || check_ptr(bp, "bp", true, 8) ||
-      check_ptr(cost, "cost", true, 8))
-    return -1;
-  if (B == 0) return 0;
-  return hip_status(noc::total_cost_params(*fam, N, B, x, u, bp, cost, params,
-                                           static_cast<hipStream_t>(stream)), "total_cost_params");
+  return args_as_minus1(total_cost_any(fam, N, B, x, u, bp, cost, params, stream));
 }
 
 }  // extern "C"

@@ -193,16 +193,18 @@ struct LqrArgs {
   const double *lam, *cu, *cxx, *cuu, *cxu, *fu, *fxx, *fuu, *fxu;
   double *ru, *Q, *R, *M;
 };
-hipError_t derivatives(const noc_family& p, const DerivArgs& a, hipStream_t s);
+// tp, here and below: the (B, 32) per-trajectory cost parameter records of the _params entry
+// points (include/noc_hip.h), or nullptr = the family's own goal, weights and bound
+hipError_t derivatives(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s);
 hipError_t final_cost_derivs(const noc_family& p, int B, const double* xN, double* grad,
-                             double* hess, hipStream_t s);
+                             double* hess, const double* tp, hipStream_t s);
 hipError_t costates(int nx, int N, int B, const double* lamT, const double* cx, const double* fx,
                     double* lam, int sequential, hipStream_t s);
 hipError_t lqr_params(const LqrArgs& a, hipStream_t s);
 hipError_t traj_feasibility(const noc_family& p, int N, int B, const double* x, const double* u,
-                            int* ok, hipStream_t s);
+                            int* ok, const double* tp, hipStream_t s);
 hipError_t total_cost(const noc_family& p, int N, int B, const double* x, const double* u,
-                      const double* bp, double* cost, hipStream_t s);
+                      const double* bp, double* cost, const double* tp, hipStream_t s);
 
 hipError_t kkt_dispatch(int nx, int nu, const KKTArgs& a, int lanes, hipStream_t stream);
 // lanes == 1: horizon-sequential solve, one trajectory per nx-lane group (kkt_group_impl.h)
@@ -228,10 +230,12 @@ hipError_t blocks_expand(const noc_family& p, const ExpandArgs& e, hipStream_t s
 int kkt_default_lanes(int nx, int nu, int N);
 int kkt_pick_lanes(int nx, int nu, int N, int B);
 
-// compact: w.A, w.B, w.Q, w.R, w.M are the compact tiled fields (block_struct.h)
+// compact: w.A, w.B, w.Q, w.R, w.M are the compact tiled fields (block_struct.h); not with tp
+// (the records need dense blocks: hipErrorInvalidValue)
 hipError_t ipm_prepare(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
-                       bool compact, hipStream_t s);
-hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, hipStream_t s);
+                       bool compact, const double* tp, hipStream_t s);
+hipError_t ipm_trial(const noc_family& p, const noc_ipm_ws& w, int mode, const double* tp,
+                     hipStream_t s);
 hipError_t ipm_rollout(const noc_family& p, const noc_ipm_ws& w, hipStream_t s);
 hipError_t ipm_prepare_main(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal,
                             bool compact, hipStream_t s);
@@ -239,7 +243,7 @@ hipError_t ipm_promote(const noc_ipm_ws& w, hipStream_t s);
 hipError_t ipm_init(const noc_ipm_ws& w, double bp0, hipStream_t s);
 // persistent whole-solve kernel (ipm_persistent.hip)
 bool ipm_solve_supported(const noc_family& p, int N, int lanes);
-// what ipm_solve / ipm_solve_params would launch, as out[NOC_PLAN_*] (ipm_plan.h)
+// what ipm_solve would launch (with_params: with tp), as out[NOC_PLAN_*] (ipm_plan.h)
 void debug_ipm_plan(const noc_family& p, int N, int Bt, int flags, bool ordered, bool with_params, int simds,
                     int* out);
 // interior-point DDP (ddp_persistent.hip)
@@ -247,7 +251,7 @@ bool ddp_supported(const noc_family& p);
 long long ddp_record_doubles(int nx, int nu);
 hipError_t ddp_solve(const noc_family& p, int N, int Bt, const double* x0, double* u,
                      double* work, int* iterations, int* passes, int* done, double bp0,
-                     int max_passes, int flags, hipStream_t s);
+                     int max_passes, int flags, const double* tp, hipStream_t s);
 // DDP building blocks (ddp_blocks.hip)
 struct DdpBwdArgs {
   int N, B;
@@ -261,31 +265,12 @@ hipError_t nonlin_rollout(const noc_family& p, int N, int B, const double* K, co
                           const double* x, const double* u, double* xn, double* un, hipStream_t s);
 int debug_phase_cycles(long long* out, int n, int reset);
 int debug_traj_times(long long* out, int n);
+// with tp always the one-wave kernel (ipm_plan.h)
 hipError_t ipm_solve(const noc_family& p, const noc_ipm_ws& w, int mode, int terminal, double bp0,
-                     int max_solves, hipStream_t s);
-// per-trajectory cost parameters (include/noc_hip.h: the _params entry points); tp: (Bt, 32)
-// records.  Dense blocks; the persistent form always runs the one-wave kernel.
+                     int max_solves, const double* tp, hipStream_t s);
+// the families that can take tp: the parametrised cost (ipm_kernels.hip); for ddp_solve also nx <= 4
 bool traj_params_supported(const noc_family& p);
-hipError_t ipm_prepare_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                              int terminal, hipStream_t s);
-hipError_t ipm_trial_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                            hipStream_t s);
-hipError_t ipm_solve_params(const noc_family& p, const noc_ipm_ws& w, const double* tp, int mode,
-                            int terminal, double bp0, int max_solves, hipStream_t s);
-// ... of interior-point DDP (ddp_persistent.hip: nx <= 4, the parametrised cost) and of the
-// building blocks that read a cost parameter (derivatives.hip: every family with that cost)
 bool ddp_params_supported(const noc_family& p);
-hipError_t ddp_solve_params(const noc_family& p, int N, int Bt, const double* x0, double* u,
-                            double* work, int* iterations, int* passes, int* done,
-                            const double* tp, double bp0, int max_passes, int flags,
-                            hipStream_t s);
-hipError_t derivatives_params(const noc_family& p, const DerivArgs& a, const double* tp, hipStream_t s);
-hipError_t final_cost_derivs_params(const noc_family& p, int B, const double* xN, double* grad,
-                                    double* hess, const double* tp, hipStream_t s);
-hipError_t traj_feasibility_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                                   int* ok, const double* tp, hipStream_t s);
-hipError_t total_cost_params(const noc_family& p, int N, int B, const double* x, const double* u,
-                             const double* bp, double* cost, const double* tp, hipStream_t s);
 // wide whole-solve kernel (ipm_wide.hip): one 4-wave workgroup per trajectory, LDS-resident
 bool ipm_wide_supported(const noc_family& p, int N);
 size_t wide_lds_bytes(const noc_family& p, int N, int W);

@@ -127,9 +127,9 @@ SIGNATURES.update({
     "noc_debug_phase_cycles": (_i, [ctypes.POINTER(ctypes.c_longlong), _i, _i]),
     "noc_debug_traj_times": (_i, [ctypes.POINTER(ctypes.c_longlong), _i]),
     "noc_ipm_solve": (_i, [_fp, _wp, _i, _i, ctypes.c_double, _i, _dp]),
-    # what a solve call would launch (added after ABI version 5: detected by symbol)
+    # what a solve call would launch (added after ABI version 5)
     "noc_debug_ipm_plan": (_i, [_fp, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), _i]),
-    # per-trajectory cost parameters (added after ABI version 5: detected by symbol)
+    # per-trajectory cost parameters (added after ABI version 5)
     "noc_traj_params_supported": (_i, [_fp, _i, _i]),
     "noc_ipm_solve_params": (_i, [_fp, _wp, _dp, _i, _i, ctypes.c_double, _i, _dp]),
     "noc_ipm_prepare_params": (_i, [_fp, _wp, _dp, _i, _i, _dp]),
@@ -147,7 +147,7 @@ SIGNATURES.update({
     "noc_ddp_solve_ex": (_i, [_fp, _i, _i] + [_dp] * 6 + [ctypes.c_double, _i, _i, _dp]),
     "noc_ddp_bwd_pass": (_i, [_i] * 4 + [_dp] * 18 + [_dp]),
     "noc_nonlin_rollout": (_i, [_fp, _i, _i] + [_dp] * 6 + [_dp]),
-    # per-trajectory cost parameters in DDP and the building blocks (detected by symbol)
+    # per-trajectory cost parameters in DDP and the building blocks
     "noc_ddp_params_supported": (_i, [_fp]),
     "noc_ddp_solve_params": (_i, [_fp, _i, _i] + [_dp] * 6 + [_dp, ctypes.c_double, _i, _i, _dp]),
     "noc_derivatives_params": (_i, [_fp, _i, _i] + [_dp] * 13 + [_dp, _dp]),
@@ -252,6 +252,18 @@ def check(rc: int, what: str, lib: Optional[ctypes.CDLL] = None) -> None:
     if rc != 0:
         msg = (lib or load()).noc_last_error().decode(errors="replace")
         raise NocError(f"{what} failed (rc={rc}): {msg}")
+
+
+def call(lib: ctypes.CDLL, base: str, *args, params=None, compact: bool = False, at: int = -1) -> None:
+    """noc_<base>(*args), checked -- or its twin: with `params` (the device address of the
+    per-trajectory records) noc_<base>_params, the address inserted before args[at] (the stream by
+    default); with `compact`, noc_<base>_compact (reported under the dense name)."""
+    name = f"noc_{base}_params" if params is not None else f"noc_{base}"
+    if params is not None:
+        args = list(args)
+        args.insert(at, params)
+    fn = getattr(lib, f"noc_{base}_compact" if compact and params is None else name)
+    check(fn(*args), name, lib)
 
 
 def ptr(t) -> Optional[int]:

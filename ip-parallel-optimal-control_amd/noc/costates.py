@@ -42,16 +42,12 @@ def final_cost_grad(ocp: OCP, final_state, hessian: bool = False, params=None):
     g = torch.empty(B, fam.nx, dtype=torch.float64, device=xN.device)
     h = torch.empty(B, fam.nx, fam.nx, dtype=torch.float64, device=xN.device) if hessian else None
     lib = _lib.load_for(fam)
+    rec = None
     if params is not None:
         from .traj_params import device_records
         rec = device_records("final_cost_grad", params, fam, B, single, xN.device)
-        _lib.check(lib.noc_final_cost_derivs_params(
-            ctypes.byref(fam.to_c()), B, xN.data_ptr(), g.data_ptr(), _lib.ptr(h), rec.data_ptr(),
-            _lib.stream_handle(xN.device)), "noc_final_cost_derivs_params", lib)
-        return (g, h) if hessian else g
-    _lib.check(lib.noc_final_cost_derivs(ctypes.byref(fam.to_c()), B, xN.data_ptr(), g.data_ptr(),
-                                         _lib.ptr(h), _lib.stream_handle(xN.device)),
-               "noc_final_cost_derivs", lib)
+    _lib.call(lib, "final_cost_derivs", ctypes.byref(fam.to_c()), B, xN.data_ptr(), g.data_ptr(),
+              _lib.ptr(h), _lib.stream_handle(xN.device), params=_lib.ptr(rec))
     if single:
         return (g[0], h[0]) if hessian else g[0]
     return (g, h) if hessian else g

@@ -176,19 +176,12 @@ def _solve(ocp, controls, initial_state, device, bp0, max_passes, flags, params=
     work = torch.empty(int(lib.noc_ddp_work_doubles(nx, nu, N, Bt)), **f64)
     i32 = dict(device=dev, dtype=torch.int32)
     its, passes, done = (torch.zeros(Bt, **i32) for _ in range(3))
-    if rec is not None:
-        tp = torch.as_tensor(rec, **f64).contiguous()
-        _lib.check(lib.noc_ddp_solve_params(ctypes.byref(fam), N, Bt, _lib.ptr(X0), _lib.ptr(U),
-                                            _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
-                                            _lib.ptr(done), _lib.ptr(tp), float(bp0),
-                                            int(max_passes), int(flags), _lib.stream_handle(dev)),
-                   "noc_ddp_solve_params", lib)
-    else:
-        _lib.check(lib.noc_ddp_solve_ex(ctypes.byref(fam), N, Bt, _lib.ptr(X0), _lib.ptr(U),
-                                        _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
-                                        _lib.ptr(done), float(bp0), int(max_passes), int(flags),
-                                        _lib.stream_handle(dev)),
-                   "noc_ddp_solve_ex", lib)
+    tp = None if rec is None else torch.as_tensor(rec, **f64).contiguous()
+    # noc_ddp_solve_ex, or noc_ddp_solve_params with the records after `done`
+    _lib.call(lib, "ddp_solve_ex" if tp is None else "ddp_solve", ctypes.byref(fam), N, Bt,
+              _lib.ptr(X0), _lib.ptr(U), _lib.ptr(work), _lib.ptr(its), _lib.ptr(passes),
+              _lib.ptr(done), float(bp0), int(max_passes), int(flags), _lib.stream_handle(dev),
+              params=_lib.ptr(tp), at=9)
     Uh, itn = U.cpu().numpy(), its.cpu().numpy()
     X = work[:Bt * (N + 1) * nx].view(Bt, N + 1, nx).cpu().numpy()
     info = dict(passes=passes.cpu().numpy(), done=done.cpu().numpy().astype(bool))

@@ -145,9 +145,7 @@ class BatchedIPM:
         if self.compact:
             raise _lib.NocError("per-trajectory parameters need dense blocks: build the engine with "
                                 "compact=False")
-        lib = self._lib
-        if not hasattr(lib, "noc_traj_params_supported") or lib.noc_traj_params_supported(
-                ctypes.byref(self.fam_c), self.N, self.lanes) != 1:
+        if self._lib.noc_traj_params_supported(ctypes.byref(self.fam_c), self.N, self.lanes) != 1:
             raise _lib.NocError("per-trajectory parameters: unsupported family or lanes "
                                 "(noc_traj_params_supported; a family with traced costs has none)")
         self._params = torch.as_tensor(rec, device=self.device).contiguous()
@@ -161,28 +159,22 @@ class BatchedIPM:
         if self.overlap:  # the roll stream must see load() + init() before its first rollout
             self.ev_main.record(torch.cuda.current_stream(self.device))
 
+    def _call(self, base: str, *args, compact_form: bool = True):
+        """noc_ipm_<base>(family, workspace, *args), or its _compact / _params twin for this
+        engine's blocks / loaded parameters (the records come right after the workspace).
+        compact_form=False: the entry point has no _compact twin (it does not read the blocks)."""
+        params = self._params.data_ptr() if self._params is not None else None
+        _lib.call(self._lib, "ipm_" + base, ctypes.byref(self.fam_c), ctypes.byref(self.ws), *args,
+                  params=params, compact=self.compact and compact_form, at=2)
+
     def prepare(self, mode: int, terminal: int):
-        if self._params is not None:
-            _lib.check(self._lib.noc_ipm_prepare_params(
-                ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
-                terminal, self._stream()), "noc_ipm_prepare_params", self._lib)
-            return
-        fn = self._lib.noc_ipm_prepare_compact if self.compact else self._lib.noc_ipm_prepare
-        _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
-                      self._stream()), "noc_ipm_prepare", self._lib)
+        self._call("prepare", mode, terminal, self._stream())
 
     def step(self, mode: int, terminal: int):
         """One device iteration.  With overlap (default) the rollouts of trajectories that start
         a barrier stage run on a second stream beside the other trajectories' Newton step."""
-        if self._params is not None:  # per-trajectory parameters: one stream, dense blocks
-            _lib.check(self._lib.noc_ipm_step_params(
-                ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
-                terminal, self.lanes, self._stream()), "noc_ipm_step_params", self._lib)
-            return
-        if not self.overlap:
-            fn = self._lib.noc_ipm_step_compact if self.compact else self._lib.noc_ipm_step
-            _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
-                          self.lanes, self._stream()), "noc_ipm_step", self._lib)
+        if self._params is not None or not self.overlap:  # per-trajectory parameters: one stream
+            self._call("step", mode, terminal, self.lanes, self._stream())
             return
         main = torch.cuda.current_stream(self.device)
         roll = self.roll_stream
@@ -190,9 +182,7 @@ class BatchedIPM:
         _lib.check(self._lib.noc_ipm_rollout(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
                                              roll.cuda_stream), "noc_ipm_rollout", self._lib)
         self.ev_roll.record(roll)
-        fn = self._lib.noc_ipm_step_main_compact if self.compact else self._lib.noc_ipm_step_main
-        _lib.check(fn(ctypes.byref(self.fam_c), ctypes.byref(self.ws), mode, terminal,
-                      main.cuda_stream), "noc_ipm_step_main", self._lib)
+        self._call("step_main", mode, terminal, main.cuda_stream)
         main.wait_event(self.ev_roll)
         _lib.check(self._lib.noc_ipm_promote(ctypes.byref(self.ws), main.cuda_stream),
                    "noc_ipm_promote", self._lib)
@@ -356,15 +346,8 @@ class BatchedIPM:
             self.ws.flags = flags | _lib.WS_RESUME
         self.ws.order = order.data_ptr() if order is not None else None
         try:
-            if self._params is not None:
-                _lib.check(self._lib.noc_ipm_solve_params(
-                    ctypes.byref(self.fam_c), ctypes.byref(self.ws), self._params.data_ptr(), mode,
-                    terminal, float(bp0), int(max_solves), self._stream()),
-                    "noc_ipm_solve_params", self._lib)
-            else:
-                _lib.check(self._lib.noc_ipm_solve(ctypes.byref(self.fam_c), ctypes.byref(self.ws),
-                                                   mode, terminal, float(bp0), int(max_solves),
-                                                   self._stream()), "noc_ipm_solve", self._lib)
+            self._call("solve", mode, terminal, float(bp0), int(max_solves), self._stream(),
+                       compact_form=False)
         finally:
             self.ws.flags = flags
             self.ws.order = None

@@ -94,16 +94,11 @@ def compute_derivatives(ocp: OCP, states, controls, bp, params=None) -> Derivati
                   fu=(nx, nu), fxx=(nx, nx, nx), fuu=(nx, nu, nu), fxu=(nx, nx, nu))
     out = {k: torch.empty((B, N) + s, **f64) for k, s in shapes.items()}
     lib = _lib.load_for(fam)
-    if params is not None:
-        rec = device_records("compute_derivatives", params, fam, B, single, x.device)
-        _lib.check(lib.noc_derivatives_params(
-            ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(), bpt.data_ptr(),
-            *(out[k].data_ptr() for k in Derivatives._fields), rec.data_ptr(),
-            _lib.stream_handle(x.device)), "noc_derivatives_params", lib)
-        return Derivatives(*(out[k] for k in Derivatives._fields))
-    _lib.check(lib.noc_derivatives(ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
-                                   bpt.data_ptr(), *(out[k].data_ptr() for k in Derivatives._fields),
-                                   _lib.stream_handle(x.device)), "noc_derivatives", lib)
+    rec = None if params is None else device_records("compute_derivatives", params, fam, B, single,
+                                                     x.device)  # NocError for an unbatched call
+    _lib.call(lib, "derivatives", ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
+              bpt.data_ptr(), *(out[k].data_ptr() for k in Derivatives._fields),
+              _lib.stream_handle(x.device), params=_lib.ptr(rec))
     d = Derivatives(*(out[k] for k in Derivatives._fields))
     return Derivatives(*(t[0] for t in d)) if single else d
 
@@ -165,16 +160,8 @@ def check_traj_feasibility(ocp: OCP, x, u, params=None):
         return ok[0] if single else ok
     ok = torch.empty(B, dtype=torch.int32, device=u.device)
     lib = _lib.load_for(fam)
-    if rec is not None:
-        _lib.check(lib.noc_check_feasibility_params(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
-                                                    u.data_ptr(), ok.data_ptr(), rec.data_ptr(),
-                                                    _lib.stream_handle(u.device)),
-                   "noc_check_feasibility_params", lib)
-        return ok.bool()
-    _lib.check(lib.noc_check_feasibility(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
-                                         u.data_ptr(), ok.data_ptr(),
-                                         _lib.stream_handle(u.device)),
-               "noc_check_feasibility", lib)
+    _lib.call(lib, "check_feasibility", ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
+              ok.data_ptr(), _lib.stream_handle(u.device), params=_lib.ptr(rec))
     ok = ok.bool()
     return ok[0] if single else ok
 
@@ -202,16 +189,9 @@ def total_cost(ocp: OCP, states, controls, bp, params=None):
     bpt = torch.as_tensor(bp, dtype=torch.float64, device=u.device).reshape(-1).expand(B).contiguous()
     cost = torch.empty(B, dtype=torch.float64, device=u.device)
     lib = _lib.load_for(fam)
-    if params is not None:
-        rec = device_records("total_cost", params, fam, B, single, u.device)
-        _lib.check(lib.noc_total_cost_params(ctypes.byref(fam.to_c()), N, B, x.data_ptr(),
-                                             u.data_ptr(), bpt.data_ptr(), cost.data_ptr(),
-                                             rec.data_ptr(), _lib.stream_handle(u.device)),
-                   "noc_total_cost_params", lib)
-        return cost
-    _lib.check(lib.noc_total_cost(ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
-                                  bpt.data_ptr(), cost.data_ptr(), _lib.stream_handle(u.device)),
-               "noc_total_cost", lib)
+    rec = None if params is None else device_records("total_cost", params, fam, B, single, u.device)
+    _lib.call(lib, "total_cost", ctypes.byref(fam.to_c()), N, B, x.data_ptr(), u.data_ptr(),
+              bpt.data_ptr(), cost.data_ptr(), _lib.stream_handle(u.device), params=_lib.ptr(rec))
     return cost[0] if single else cost
 
 
