@@ -182,7 +182,9 @@ typedef struct noc_family {
                               retry recomputes the LQ blocks from x, u: the workspace's A, B, Q, R,
                               M are not read, so the resume may follow either driver (they hold
                               noc_ipm_solve's compact records, or the dense / compact fields of the
-                              launch-per-phase entry points) */
+                              launch-per-phase entry points), at any of its phases: ROLLED resumes
+                              as LINEARIZE, ROLLOUT_PENDING as ROLLOUT.  The hand-off works in the
+                              other direction too: see noc_ipm_step */
 #define NOC_WS_NO_REPEAT_SKIP 4 /* flags bit: recompute every retry of the par inner loop, even the
                               repeats at the rp clip that the solvers otherwise account without
                               recomputing (ws->repeats; same results bit for bit either way) */
@@ -225,7 +227,12 @@ int noc_ipm_prepare(const noc_family* fam, const noc_ipm_ws* ws, int mode, int t
 /* trial point, gain ratio, regularisation update, accept, stop test, barrier schedule. */
 int noc_ipm_trial(const noc_family* fam, const noc_ipm_ws* ws, int mode, void* stream);
 /* one device iteration: prepare + noc_kkt_solve(active = phase SOLVE) + trial.  lanes must be 0
- * or ws->lanes (the workspace's tiled layout fixes it); anything else is rejected. */
+ * or ws->lanes (the workspace's tiled layout fixes it); anything else is rejected.
+ * The loop of these calls (and of the two-stream and _compact / _params forms) may continue a
+ * workspace that a capped noc_ipm_solve left, whichever kernel that ran: a trajectory it left at
+ * SOLVE carries kkt_active = 0, which marks its blocks as not in this workspace, and prepare
+ * rebuilds A, B, Q, R, M, r, cx, cu, lam, P and reg for it from x, u, bp, rp and gnorm (the same
+ * doubles a linearisation at that point gives) without touching it, inner, cost, hu or gnorm. */
 int noc_ipm_step(const noc_family* fam, const noc_ipm_ws* ws, int mode, int terminal, int lanes,
                  void* stream);
 /* Two-stream form of one iteration (rollouts overlap the other trajectories' Newton step):

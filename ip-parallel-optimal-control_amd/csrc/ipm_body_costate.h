@@ -4,7 +4,10 @@
 // including kernel in scope).  Not a stand-alone header (no include guard on purpose).
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = tid / L, l = tid % L;
-  if (b >= w.Bt || w.phase[b] != NOC_PHASE_LINEARIZE) return;  // uniform per segment
+  if (b >= w.Bt || !builds_blocks(w, b)) return;  // uniform per segment
+  // a retry handed over by a persistent launch (ipm_schedule.h: blocks_missing): lam, r, P and
+  // reg are rebuilt, the iteration's cost, |Hu|, ||cu|| and retry count stay as that launch left them
+  const bool handed_over = w.phase[b] == NOC_PHASE_SOLVE;
   Fam<KIND, NX, NU> f(prm);
   const int N = w.N;
   const Chunks ch(N, L);
@@ -136,6 +139,10 @@
   double P[NX * NX];
   f.final_hess(xN, P);  // hessian(final_cost) (S:66)
   gstore<NX * NX>(w.P + (size_t)b * NX * NX, P);
+  if (handed_over) {
+    w.reg[b] = candidate_reg(mode, w.rp[b], w.gnorm[b]);
+    return;
+  }
   w.cost[b] = cost + f.final_cost(xN);   // total_cost(x, u, bp) (P:142)
   w.hu[b] = hu;                          // max |Hu| (P:158)
   const double gn = sqrt(g2s);           // ||cu||_F (P:116)

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void linearize_kernel(noc_family prm, noc_ipm_
   const int b = (int)(t / ((long long)ch.cmax * L));
   const int rem = (int)(t % ((long long)ch.cmax * L));
   const int j = rem / L, l = rem % L;
-  if (j >= ch.len(l) || w.phase[b] != NOC_PHASE_LINEARIZE) return;
+  if (j >= ch.len(l) || !builds_blocks(w, b)) return;
   const int k = ch.start(l) + j;
   const size_t tn = (size_t)b * N + k;
   Fam<KIND, NX, NU> f(prm);
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(noc_family prm, noc_ipm_w
   const int b = (int)(t / ((long long)ch.cmax * L));
   const int rem = (int)(t % ((long long)ch.cmax * L));
   const int j = rem / L, l = rem % L;
-  if (j >= ch.len(l) || w.phase[b] != NOC_PHASE_LINEARIZE) return;
+  if (j >= ch.len(l) || !builds_blocks(w, b)) return;
   const int k = ch.start(l) + j;
   const size_t tn = (size_t)b * N + k;
   Fam<KIND, NX, NU> f(prm);

@@ -40,6 +40,22 @@ NOC_DEV int resume_phase(int ph) {
   return ph;
 }
 
+// The hand-off marker.  A persistent launch that stops at its solve cap leaves kkt_active = 0
+// (IpmState::store), while the launch-per-phase driver never leaves a SOLVE trajectory without
+// kkt_active = 1 (mark_solve_kernel; the trial kernel does not touch it).  So (SOLVE,
+// kkt_active == 0) says "this trajectory's LQ blocks, cx, cu, lam, r, P and reg are not in this
+// workspace": the launch-per-phase prepare rebuilds them from x, u, bp, rp, gnorm before its
+// KKT scan reads them (ipm_kernels.hip), leaving it, inner, cost, hu and gnorm as they are.
+NOC_DEV bool blocks_missing(const noc_ipm_ws& w, int b, int ph) {
+  return ph == NOC_PHASE_SOLVE && w.kkt_active[b] == 0;
+}
+// The trajectories a launch-per-phase prepare builds blocks for: a new Newton iteration, or a
+// retry that a persistent launch handed over
+NOC_DEV bool builds_blocks(const noc_ipm_ws& w, int b) {
+  const int ph = w.phase[b];
+  return ph == NOC_PHASE_LINEARIZE || blocks_missing(w, b, ph);
+}
+
 // Where the solve continues after an accept step: the next barrier stage's rollout (P:243-245;
 // NOC_WS_ONE_STAGE: newton_oc runs a single stage), a new linearisation, or a retry on the same
 // blocks with the new regularisation

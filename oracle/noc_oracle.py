@@ -328,8 +328,9 @@ def seq_solution(prob, X, U, bp, rp):
     return dx, du, pred, feas, L["r"]
 
 
-def seq_newton_oc(prob, U, x0, bp, max_iter=100000):
-    """S:108-177 -- one accept/reject per iteration; stops when |Hu|inf < 1e-4 AND bwd feasible."""
+def seq_newton_oc(prob, U, x0, bp, max_iter=100000, trace=None):
+    """S:108-177 -- one accept/reject per iteration; stops when |Hu|inf < 1e-4 AND bwd feasible.
+    trace: a list that receives one dict per iteration (the accept test's inputs and outcome)."""
     X = rollout(prob.dynamics, U, x0)
     mu, nu_ = 1.0, 2.0
     t = 0
@@ -350,15 +351,18 @@ def seq_newton_oc(prob, U, x0, bp, max_iter=100000):
         else:
             mu = mu * nu_
             nu_ = 2 * nu_
+        if trace is not None:
+            trace.append(dict(it=t, pred=pred, gain=gain, success=accept, feas=bpf, rp=mu, rinc=nu_,
+                              cost=cost, new_cost=new_cost, hu=Hu_norm, bp=bp))
         t += 1
     return X, U, t
 
 
-def seq_interior_point_optimal_control(prob, U, x0):
-    """S:180-202 barrier schedule 0.1 / 5^k while bp > 1e-4."""
+def seq_interior_point_optimal_control(prob, U, x0, trace=None):
+    """S:180-202 barrier schedule 0.1 / 5^k while bp > 1e-4.  trace: see seq_newton_oc."""
     bp, total = 0.1, 0
     while bp > 1e-4:
-        _, U, it = seq_newton_oc(prob, U, x0, bp)
+        _, U, it = seq_newton_oc(prob, U, x0, bp, trace=trace)
         bp /= 5
         total += it
     return U, total
@@ -404,8 +408,8 @@ def par_newton_oc(prob, U, x0, bp, terminal="final_cost", trace=None):
             inner += 1
             if trace is not None:
                 trace.append(dict(it=it, inner=inner, reg=reg, pred=pred, gain=gain,
-                                  success=success, rp=rp, cost=cost, new_cost=new_cost, hu=Hn,
-                                  bp=bp))
+                                  success=success, feas=feas, rp=rp, rinc=r_inc, cost=cost,
+                                  new_cost=new_cost, hu=Hn, bp=bp))
             if success or inner > 500:                                  # P:177-182
                 break
         X, U, Hu_norm = tX, tU, Hn                                      # P:184-188
